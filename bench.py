@@ -7,15 +7,19 @@ CamVid-shaped inputs.  "480x360" images are resized to the script's --crop-size 
 as the reference's loaders do: the network input is 16x3x288x480 fp32.
 One step = one batch through the whole path; inputs are resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly K steps once and prints the headline
+(value, ms_per_step = milliseconds of one timed step).  --dump-outputs DIR writes what the timed path returned for its last
+batch (DIR/labels.npy, DIR/kld.npy, float32); inputs and weights are seeded, so two builds can be compared output for output.
+--full adds everything else (the timed loop repeated --repeats times, median reported), among it:
   roofline     dominant kernel = eesp_dw_exp (K2 + K3 of the stride-1 EESP blocks in one launch): matrix FLOPs per launch /
                mean launch time against the fp32 MFMA peak (+ its bytes against the HBM roof), measured with HIP events on the
                launch stream inside this process; roofline_k2 = the standalone K2 launches that remain (HBM).
   cpu_baseline the CPU oracle (oracle/, a port of the reference's torch path) timed on the host cores on a
                bounded sample of the same workload (rank 0, N=1 only).
+  single_in_flight, the 3-source / Cityscapes-shape label passes, train / eval / supervised steps, ASPP head, loader I/O.
 """
 import argparse
 import json
@@ -488,6 +492,10 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--full', action='store_true', help='beyond the headline: repeated timing, single-in-flight latency, kernel '
+                    'rooflines, the extra workloads and the CPU baseline (the --no-* options below trim this set)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write the label map and KL '
+                    'uncertainty map of the last timed batch as DIR/labels.npy and DIR/kld.npy (float32, rank 0)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-train', action='store_true', help='skip the extra train-step field')
     ap.add_argument('--no-three-source', action='store_true', help='skip the extra 3-source label pass field (BASELINE configs[2])')
@@ -501,8 +509,9 @@ def main():
                     'each other and the per-kernel averages stop describing the kernels)')
     ap.add_argument('--group', type=int, default=2, help='consecutive batches of 16 that one launch of a lane labels (PipelinedLabelPass '
                     'group): 2 = 32 images per launch, 3 lanes; images are independent, results are per batch')
-    ap.add_argument('--repeats', type=int, default=5, help='the timed loop of --steps steps is run this many times inside one invocation '
-                    '(each bracketed by barrier + synchronize); ms_per_step / value are the MEDIAN repetition, min / max are reported beside it')
+    ap.add_argument('--repeats', type=int, default=None, help='the timed loop of --steps steps is run this many times inside one invocation '
+                    '(each bracketed by barrier + synchronize); ms_per_step / value are the MEDIAN repetition, min / max are reported beside it '
+                    '(default 1, with --full 5)')
     ap.add_argument('--profile-pass', action='store_true', help='only the timed label passes: no K2 re-issues, no extra fields '
                     '(for rocprofv3 --kernel-trace --stats: the CSV then holds in-pass launches only; tools/per_kernel.py)')
     ap.add_argument('--profile-batch', type=int, default=0, help='with --profile-pass only: images per launch (kernel scaling study; '
@@ -579,20 +588,28 @@ def main():
         torch.cuda.synchronize()
 
     def run(steps):
+        """`steps` batches through the pipeline; returns the last batch's outputs (labels, kld), valid until the next submit."""
         for _ in range(steps):
             plp(xs[plp.next_lane])
-        list(plp.flush())
+        outs = list(plp.flush())
+        return outs[-1] if outs else None
 
     # warm-up: at least W steps, rounded up to whole launches (a partly filled lane would be labelled by a shorter launch)
     run(-(-args.warmup // group) * group)
-    repeats = max(1, 1 if args.profile_pass else args.repeats)
+    repeats = args.repeats if args.repeats is not None else (5 if args.full else 1)
+    repeats = max(1, 1 if args.profile_pass else repeats)
     samples = []
     for _ in range(repeats):
         barrier()
         t0 = time.perf_counter()
-        run(args.steps)                                    # EXACTLY K steps, pipeline fill and drain included
+        last = run(args.steps)                             # EXACTLY K steps, pipeline fill and drain included
         barrier()
         samples.append(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0 and last is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in zip(('labels', 'kld'), last):       # uint8 (16, H, W) class ids, fp32 (16, H, W) KL(pred || aux)
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), t.float().cpu().numpy())
     if world > 1:
         t = torch.tensor(samples, device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)           # every repetition: the slowest rank's time
@@ -604,6 +621,40 @@ def main():
             print(json.dumps({'metric': 'profile-pass (no roofline / extras)', 'value': round(BATCH * world * args.steps / elapsed, 2),
                               'unit': 'images/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
                               'batches_in_flight': depth, 'batches_per_launch': group}))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    out = None
+    if rank == 0:
+        out = {
+            'metric': 'images/sec pseudo-label gen, ESPDNet-UE s=2.0 480x360(->288x480) bs=16',
+            'value': round(BATCH * world * args.steps / elapsed, 2),
+            'unit': 'images/s',
+            'n_gpus': world,
+            'steps': args.steps,
+            'warmup': args.warmup,
+            'ms_per_step': round(elapsed / args.steps * 1e3, 4),
+            'repeats': repeats,
+            'ms_per_step_min_max': [round(min(samples) / args.steps * 1e3, 4), round(max(samples) / args.steps * 1e3, 4)],
+            'timing_note': 'each repetition = %d steps between barrier + synchronize, pipeline fill and drain included; value / ms_per_step = '
+                           'the median repetition' % args.steps,
+            'higher_is_better': True,
+            'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': 'f32',
+            'data': 'synthetic',
+            'config': {'workload': 'BASELINE configs[1]: ESPDNet-UE s=2.0 C=13 single-source pseudo-label gen '
+                                   '(forward + pred+0.5aux argmax + KL uncertainty + histogram), bs=16/GPU, '
+                                   '16x3x288x480 fp32, hipGraph replay' + (' off' if args.no_graph else '') +
+                                   ', %d launches in flight per GPU, %d consecutive batches of 16 per launch' % (depth, group),
+                       'per_gpu_batch': BATCH, 'batches_in_flight': depth, 'batches_per_launch': group, 'input': [BATCH, 3, H, W],
+                       'classes': CLASSES,
+                       'sharding': 'image list sharded by rank, no data-path collective'},
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
         if world > 1:
             dist.destroy_process_group()
         return
@@ -913,30 +964,7 @@ def main():
 
     if rank == 0:
         ip1 = in_pass.get(1, {})
-        out = {
-            'metric': 'images/sec pseudo-label gen, ESPDNet-UE s=2.0 480x360(->288x480) bs=16',
-            'value': round(BATCH * world * args.steps / elapsed, 2),
-            'unit': 'images/s',
-            'n_gpus': world,
-            'steps': args.steps,
-            'warmup': args.warmup,
-            'ms_per_step': round(elapsed / args.steps * 1e3, 4),
-            'repeats': repeats,
-            'ms_per_step_min_max': [round(min(samples) / args.steps * 1e3, 4), round(max(samples) / args.steps * 1e3, 4)],
-            'timing_note': 'each repetition = %d steps between barrier + synchronize, pipeline fill and drain included; value / ms_per_step = '
-                           'the median repetition' % args.steps,
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'f32',
-            'data': 'synthetic',
-            'config': {'workload': 'BASELINE configs[1]: ESPDNet-UE s=2.0 C=13 single-source pseudo-label gen '
-                                   '(forward + pred+0.5aux argmax + KL uncertainty + histogram), bs=16/GPU, '
-                                   '16x3x288x480 fp32, hipGraph replay' + (' off' if args.no_graph else '') +
-                                   ', %d launches in flight per GPU, %d consecutive batches of 16 per launch' % (depth, group),
-                       'per_gpu_batch': BATCH, 'batches_in_flight': depth, 'batches_per_launch': group, 'input': [BATCH, 3, H, W],
-                       'classes': CLASSES,
-                       'sharding': 'image list sharded by rank, no data-path collective'},
+        out.update({
             # `roofline` = the dominant kernel (the fused K2 + K3 launch) at its IN-PASS launch time; `roofline_k2` = the standalone K2
             # launches that remain (the strided blocks); `roofline_family` = all thirteen against their bytes, for continuity with
             # rounds 1-3 (whose `roofline` was the thirteen standalone K2 launches: 0.30 of the HBM roof)
@@ -986,7 +1014,7 @@ def main():
                               'achieved': round(PATH_BYTES_PER_IMAGE * BATCH * args.steps / elapsed / 1e9, 1),
                               'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                               'frac': round(PATH_BYTES_PER_IMAGE * BATCH * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 4)},
-        }
+        })
         pk = os.path.join(ROOT, 'profiles', newest(['r05_per_kernel.json', 'r04_per_kernel.json', 'r03_per_kernel.json']) or 'none')
         if os.path.exists(pk):
             # per-kernel table of one label pass (us, MB, fraction of the HBM roof), from a rocprofv3 --kernel-trace --stats run of

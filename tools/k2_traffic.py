@@ -5,8 +5,8 @@ Corrections per /opt/skills/guides/MI355X_MICROARCH.md, section HBM: both counte
 the 128-B requests of wide coalesced reads at 64 B, so it is doubled; WRITE_SIZE is exact for 16-B-per-lane stores.
 Usage: python tools/k2_traffic.py <dir with FETCH_SIZE_counter_collection.csv and WRITE_SIZE_...> <out.json>
 The collecting commands (GPU box):
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d DIR -o FETCH_SIZE -- python3 bench.py --steps 3 --warmup 1 --no-graph --no-cpu-baseline
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d DIR -o WRITE_SIZE -- python3 bench.py --steps 3 --warmup 1 --no-graph --no-cpu-baseline
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d DIR -o FETCH_SIZE -- python3 bench.py --full --steps 3 --warmup 1 --no-graph --no-cpu-baseline
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d DIR -o WRITE_SIZE -- python3 bench.py --full --steps 3 --warmup 1 --no-graph --no-cpu-baseline
 """
 import csv, json, sys
 d, out = sys.argv[1], sys.argv[2]

@@ -3,7 +3,7 @@
 corrected like tools/k2_traffic.py (KiB -> bytes; FETCH_SIZE x2 on gfx950; WRITE_SIZE exact).  FETCH_SIZE x2 over-counts narrow
 reads (only 128-B requests are tallied at half), so the read figure is an upper bound for kernels with scalar / 4-byte loads.
 Usage: python tools/pass_traffic.py <dir> <out.json>; the collecting commands (GPU box):
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d DIR -o FETCH_SIZE -- python3 bench.py --steps 2 --warmup 1 --in-flight 1 --no-graph --no-cpu-baseline --no-train --no-aspp --no-io --no-bs64
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d DIR -o FETCH_SIZE -- python3 bench.py --full --steps 2 --warmup 1 --in-flight 1 --no-graph --no-cpu-baseline --no-train --no-aspp --no-io --no-bs64
   (same with WRITE_SIZE)"""
 import collections, csv, json, sys
 d, out = sys.argv[1], sys.argv[2]
