@@ -450,10 +450,11 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void bn_train_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ gy,
                                                                  const float* __restrict__ scale, const float* __restrict__ shift,
                                                                  const float* __restrict__ alpha, const float* __restrict__ p,
-                                                                 const float* __restrict__ q, int C, int L, float* __restrict__ gz) {
+                                                                 const float* __restrict__ q, long long planes, int C, int L,
+                                                                 float* __restrict__ gz) {
     const long long plane = (long long)blockIdx.z * gridDim.y + blockIdx.y;      // n * C + c
     const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= L) return;
+    if (plane >= planes || t >= L) return;              // the (y, z) plane split rounds up past planes > 65535
     const int c = (int)(plane % C);
     const float sc = scale[c], sh = shift[c], pc = p[c], qc = q[c];
     const bool act = alpha != nullptr;
@@ -626,8 +627,8 @@ extern "C" int mspl_bn_train_prelu_bwd_apply(const float* z, const float* gy, co
     MSPL_REQUIRE(planes <= 65535ll * 65535ll, MSPL_ERR_BAD_SHAPE, "bn_train_prelu_bwd_apply: too many planes");
     const int gy_ = planes < 65535 ? (int)planes : 65535;
     const dim3 grid((unsigned)ceil_div(L, 256), (unsigned)gy_, (unsigned)ceil_div64(planes, gy_));
-    if (vec) hipLaunchKernelGGL(bn_train_bwd_apply_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, z, gy, scale, shift, alpha, p, q, C, L, gz);
-    else hipLaunchKernelGGL(bn_train_bwd_apply_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, z, gy, scale, shift, alpha, p, q, C, L, gz);
+    if (vec) hipLaunchKernelGGL(bn_train_bwd_apply_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, z, gy, scale, shift, alpha, p, q, (long long)planes, C, L, gz);
+    else hipLaunchKernelGGL(bn_train_bwd_apply_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, z, gy, scale, shift, alpha, p, q, (long long)planes, C, L, gz);
     MSPL_CHECK_LAUNCH("bn_train_prelu_bwd_apply");
     return MSPL_OK;
 }

@@ -1708,11 +1708,11 @@ extern "C" int mspl_sum_n(const float* const* srcs, int32_t n, int64_t count, fl
 namespace mspl {
 // sum of n tensors + a per-plane constant (mul * pc[plane]): the gradient of a global average pool is constant over its plane, so the
 // sum of an encoder output's gradients takes it as N * C values instead of a full-size tensor somebody wrote only to have it added
-__global__ __launch_bounds__(256) void sum_n_planes_kernel(SumSrcs srcs, int n, const float* __restrict__ pc, float mul, int HW4,
-                                                           float* __restrict__ out) {
+__global__ __launch_bounds__(256) void sum_n_planes_kernel(SumSrcs srcs, int n, const float* __restrict__ pc, float mul, int planes,
+                                                           int HW4, float* __restrict__ out) {
     const int plane = blockIdx.z * gridDim.y + blockIdx.y;
     const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= HW4) return;
+    if (plane >= planes || q >= HW4) return;           // the (y, z) plane split rounds up past planes > 65535
     const int64_t i = (int64_t)plane * HW4 + q;
     const float c = mul * pc[plane];
     float4 a = reinterpret_cast<const float4*>(srcs.p[0])[i];
@@ -1740,7 +1740,7 @@ extern "C" int mspl_sum_n_planes(const float* const* srcs, int32_t n, const floa
     MSPL_REQUIRE((((uintptr_t)out) & 15) == 0, MSPL_ERR_UNSUPPORTED, "sum_n_planes: unaligned destination");
     const int gy = planes < 65535 ? planes : 65535;
     hipLaunchKernelGGL(mspl::sum_n_planes_kernel, dim3((unsigned)ceil_div(HW / 4, 256), (unsigned)gy, (unsigned)ceil_div(planes, gy)), dim3(256), 0,
-                       (hipStream_t)stream, s, n, plane_const, mul, HW / 4, out);
+                       (hipStream_t)stream, s, n, plane_const, mul, planes, HW / 4, out);
     MSPL_CHECK_LAUNCH("sum_n_planes");
     return MSPL_OK;
 }

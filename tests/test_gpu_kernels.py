@@ -579,3 +579,56 @@ def test_pyrpool_merge_from_kept_branches(cfg):
     want = F.conv2d(a, mw, None, 1, 1, 1, P)
     got = ops.pyrpool_merge(z.to(DEV), sc.to(DEV), sh.to(DEV), al.to(DEV), mw.to(DEV))
     torch.testing.assert_close(got.cpu(), want, rtol=1e-5, atol=1e-5)
+
+
+def _split_slots(planes):
+    """Plane slots of the launchers' (y, z) grid split: gy = min(planes, 65535), gz = ceil(planes / gy)."""
+    gy = min(planes, 65535)
+    return gy * (-(-planes // gy))
+
+
+@pytest.mark.parametrize('planes', [65535, 65536, 65541, 131071])
+@pytest.mark.parametrize('HW', [4, 8])
+@pytest.mark.parametrize('n', [1, 3, 8])
+def test_sum_n_planes_past_one_grid_row_of_planes(planes, HW, n):
+    """mspl_sum_n_planes (FanOutFn's backward) at N * C > 65535, where the plane split over (blockIdx.y, blockIdx.z) rounds up: the sum
+    against float64, and the region just past `out` (as many planes as the surplus workgroups would address) left untouched."""
+    import ctypes
+    from mspl_amd.ops import _p, _stream, check, lib
+    g = torch.Generator().manual_seed(planes + 10 * HW + n)
+    srcs = [torch.randn(planes, HW, generator=g) for _ in range(n)]
+    pc = torch.randn(planes, generator=g)
+    want = torch.stack([s.double() for s in srcs]).sum(0) + 0.75 * pc.double()[:, None]
+    canary = (_split_slots(planes) - planes + 1) * HW
+    buf = torch.full((planes * HW + canary,), 12345.0, device=DEV)
+    dsrcs = [s.to(DEV) for s in srcs]
+    dpc = pc.to(DEV)
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in dsrcs])
+    check(lib.mspl_sum_n_planes(ptrs, n, _p(dpc), 0.75, planes, HW, _p(buf), _stream()))
+    torch.cuda.synchronize()
+    got = buf[:planes * HW].view(planes, HW).cpu().double()
+    torch.testing.assert_close(got, want, rtol=1e-6, atol=1e-5)
+    assert bool((buf[planes * HW:] == 12345.0).all()), 'sum_n_planes wrote past its output'
+
+
+@pytest.mark.parametrize('N,C', [(65535, 1), (16384, 4), (21847, 3), (131071, 1)])
+@pytest.mark.parametrize('HW', [4, 5])
+def test_bn_train_prelu_bwd_apply_past_one_grid_row_of_planes(N, C, HW):
+    """mspl_bn_train_prelu_bwd_apply at N * C > 65535 (same (y, z) plane split; HW = 5 takes the scalar form): gz = p z + q +
+    (u > 0 ? gy : alpha gy) * scale with u = z * scale + shift, against float64, and nothing written past gz."""
+    from mspl_amd.ops import _p, _stream, check, lib
+    g = torch.Generator().manual_seed(N + HW)
+    z, gy = torch.randn(N, C, HW, generator=g), torch.randn(N, C, HW, generator=g)
+    sc, sh, al = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1, torch.rand(C, generator=g) * 0.3
+    p, q = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    planes = N * C
+    canary = (_split_slots(planes) - planes + 1) * HW
+    buf = torch.full((planes * HW + canary,), 12345.0, device=DEV)
+    dev = [t.to(DEV) for t in (z, gy, sc, sh, al, p, q)]
+    check(lib.mspl_bn_train_prelu_bwd_apply(*[_p(t) for t in dev], N, C, HW, _p(buf), _stream()))
+    torch.cuda.synchronize()
+    v = lambda t: t.double().view(1, C, 1)
+    u = z.double() * v(sc) + v(sh)               # (the kernel's fmaf: one rounding of the exact value, whose sign this is)
+    want = z.double() * v(p) + v(q) + torch.where(u > 0, gy.double(), v(al) * gy.double()) * v(sc)
+    torch.testing.assert_close(buf[:planes * HW].view(N, C, HW).cpu().double(), want, rtol=1e-5, atol=1e-5)
+    assert bool((buf[planes * HW:] == 12345.0).all()), 'bn_train_prelu_bwd_apply wrote past its output'
