@@ -647,6 +647,59 @@ int mspl_transpose_weights(const void* seg_table, const void* block_table, int32
 int mspl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                    float eps, float weight_decay, int32_t step, void* stream);
 
+/* ---- train-time loader transforms ------------------------------------------------------------------------------------
+ * Replace, for a whole batch of decoded uint8 images of one source size, the train transforms of the segmentation loaders:
+ *   data_loader/segmentation/greenhouse.py:211-219  GreenhouseRGBDSegmentation: RandomScale -> Resize -> RandomFlip -> Normalize
+ *   data_loader/segmentation/greenhouse.py:118-125  GreenhouseSegmentation:     RandomCrop -> RandomFlip -> Normalize
+ *   data_loader/segmentation/camvid.py:95-104       RandomScale -> RandomCrop(ignore_idx) -> Resize -> RandomFlip -> Normalize
+ *   data_loader/segmentation/cityscapes.py:109-117  RandomScale -> RandomCrop -> RandomFlip -> Normalize
+ * i.e. transforms/segmentation/data_transforms.py:49-136,191-212: RandomScale resizes rgb with Image.ANTIALIAS (= LANCZOS), the
+ * label with NEAREST and depth with BILINEAR; RandomCrop pads by (pad_w, pad_h) on both sides (fill 0, labels ignore_idx) and
+ * crops `size` at (i, j); Resize is BILINEAR / NEAREST; RandomFlip mirrors; Normalize / Tensorize as mspl_preprocess_u8_fwd.
+ * Pillow's arithmetic is reproduced bit for bit (a pass whose size does not change is skipped, an unchanged size is a copy).
+ * The random draws stay with the caller (host); each image's outcome travels in one record.
+ *
+ * mspl_resample_ksize_filter / mspl_resample_coeffs_filter: mspl_resample_ksize / mspl_resample_coeffs for filter
+ * MSPL_FILTER_LANCZOS (Resample.c lanczos_filter, support 3) or MSPL_FILTER_BILINEAR (the tables above, unchanged). */
+#define MSPL_FILTER_LANCZOS 1
+#define MSPL_FILTER_BILINEAR 2
+int mspl_resample_ksize_filter(int32_t in_size, int32_t out_size, int32_t filter);
+int mspl_resample_coeffs_filter(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* kk);
+
+/* A resampling table on the device: int32 [stride, then per output index: first source index, tap count, stride - 2 weights]
+ * (stride = 2 + ksize; the bounds / kk of mspl_resample_coeffs_filter interleaved).  A nearest table: int32 [out] from
+ * mspl_nearest_index.  Per image (112 bytes): the tables of ITS sizes; a table may be NULL where its two sizes are equal (and is
+ * not read in crop mode for the out_* / near_out_* ones, nor for depth / label when those are not given). */
+typedef struct mspl_train_rec {
+    const int32_t* scale_x;       /* LANCZOS  Ws -> sw   (rgb, RandomScale) */
+    const int32_t* scale_y;       /* LANCZOS  Hs -> sh */
+    const int32_t* dscale_x;      /* BILINEAR Ws -> sw   (depth, RandomScale) */
+    const int32_t* dscale_y;      /* BILINEAR Hs -> sh */
+    const int32_t* out_x;         /* BILINEAR sw -> W    (Resize, rgb and depth) */
+    const int32_t* out_y;         /* BILINEAR sh -> H */
+    const int32_t* near_x;        /* NEAREST  Ws -> sw   (label, RandomScale) */
+    const int32_t* near_y;        /* NEAREST  Hs -> sh */
+    const int32_t* near_out_x;    /* NEAREST  sw -> W    (label, Resize) */
+    const int32_t* near_out_y;    /* NEAREST  sh -> H */
+    int32_t sh, sw;               /* size after RandomScale (= Hs, Ws without it) */
+    int32_t pad_h, pad_w;         /* RandomCrop padding on each side */
+    int32_t crop_i, crop_j;       /* RandomCrop origin (row, column) in the padded image */
+    int32_t flip;                 /* RandomFlip: 1 = mirror */
+    int32_t reserved;             /* 0 */
+} mspl_train_rec_t;
+/* Workspace bytes for N images scaled to at most max_sh x max_sw (rgb, and depth when with_depth != 0). */
+int64_t mspl_train_transform_workspace_bytes(int32_t N, int32_t max_sh, int32_t max_sw, int32_t with_depth);
+/* rgb (N,Hs,Ws,3), label (N,Hs,Ws) or NULL, depth (N,Hs,Ws) or NULL: uint8 device tensors.  recs_host: the N records in host
+ * memory (checked here, never dereferenced on the device); recs_dev: a device copy of the same N records (what the kernels read;
+ * the caller issues its copy on `stream` before this call).  crop != 0: RandomCrop to (H, W) (no Resize: in every reference
+ * pipeline the crop IS the size), crop == 0: Resize to (H, W).  mean/std: 3 device floats or both NULL (Tensorize).
+ * ws: mspl_train_transform_workspace_bytes(N, max_sh, max_sw, depth != NULL) bytes.  Outputs (N,3,H,W) fp32, (N,H,W) int64
+ * (skipped when label is NULL), (N,1,H,W) fp32 (skipped when depth is NULL).  At most three launches, no host synchronisation. */
+int mspl_train_transform_fwd(const uint8_t* rgb, const uint8_t* label, const uint8_t* depth, int32_t N, int32_t Hs, int32_t Ws,
+                             int32_t H, int32_t W, int32_t crop, int32_t ignore_idx, const mspl_train_rec_t* recs_host,
+                             const mspl_train_rec_t* recs_dev, const float* mean, const float* stdv, uint8_t* ws, int32_t max_sh,
+                             int32_t max_sw, float* out_rgb, int64_t* out_label, float* out_depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,16 @@ class Epilogue(ctypes.Structure):
                 ('struct_size', ctypes.c_uint32), ('flags', ctypes.c_uint32)]
 
 
+class TrainRec(ctypes.Structure):
+    """mspl_train_rec_t: one image's outcome of the train transforms' random draws, with its device tables."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ('scale_x', 'scale_y', 'dscale_x', 'dscale_y', 'out_x', 'out_y', 'near_x', 'near_y',
+                                               'near_out_x', 'near_out_y')] + \
+               [(n, c_i32) for n in ('sh', 'sw', 'pad_h', 'pad_w', 'crop_i', 'crop_j', 'flip', 'reserved')]
+
+
+FILTER_LANCZOS = 1              # MSPL_FILTER_LANCZOS
+FILTER_BILINEAR = 2             # MSPL_FILTER_BILINEAR
+
 ABI_VERSION = 3                 # include/mspl_hip.h: mspl_abi_version()
 LAUNCH_THROUGHPUT = 1           # MSPL_LAUNCH_THROUGHPUT
 LAUNCH_K2_STREAM_OFF = 2        # MSPL_LAUNCH_K2_STREAM_OFF
@@ -141,6 +151,10 @@ SIGNATURES = {
     'mspl_preprocess_u8_fwd': [ctypes.c_void_p] + [c_i32] * 6 + [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p,
                                ctypes.c_void_p, c_i32] + [ctypes.c_void_p] * 6,
     'mspl_resize_label_fwd': [ctypes.c_void_p] + [c_i32] * 5 + [ctypes.c_void_p] * 5,
+    'mspl_resample_ksize_filter': [c_i32, c_i32, c_i32],
+    'mspl_resample_coeffs_filter': [c_i32, c_i32, c_i32, ctypes.c_void_p, ctypes.c_void_p],
+    'mspl_train_transform_workspace_bytes': [c_i32] * 4,
+    'mspl_train_transform_fwd': [ctypes.c_void_p] * 3 + [c_i32] * 7 + [ctypes.c_void_p] * 5 + [c_i32] * 2 + [ctypes.c_void_p] * 4,
     'mspl_bn_batch_stats_fwd': [c_f32p, c_i32, c_i32, c_i32, ctypes.c_float, ctypes.c_float] + [ctypes.c_void_p] * 6,
     'mspl_sgd_step': [c_f32p, c_f32p, c_f32p, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_i32, ctypes.c_void_p],
     'mspl_bn_batch_stats_fold_fwd': [c_f32p, c_i32, c_i32, c_i32, ctypes.c_float, ctypes.c_float] + [c_f32p] * 4 + [ctypes.c_void_p] + [c_f32p] * 4 + [ctypes.c_void_p],
@@ -185,6 +199,7 @@ def _load():
     lib.mspl_bn_fused_workspace_bytes.restype = ctypes.c_int64
     lib.mspl_eesp_dw_exp_next_pack_floats.restype = ctypes.c_int64
     lib.mspl_label_epilogue_hist_workspace_bytes.restype = ctypes.c_int64
+    lib.mspl_train_transform_workspace_bytes.restype = ctypes.c_int64
     lib.mspl_png_writer_create.restype = ctypes.c_void_p          # a handle
     lib.mspl_png_writer_submit.restype = ctypes.c_int64           # a ticket (or a negative status)
     lib.mspl_version.restype = ctypes.c_char_p

@@ -91,26 +91,47 @@ static inline double bilinear_filter(double x) {
     return x < 1.0 ? 1.0 - x : 0.0;
 }
 
+// Resample.c sinc_filter / lanczos_filter (Image.LANCZOS, the reference's Image.ANTIALIAS): same operation order as Pillow's.
+static inline double sinc_filter(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+
+static inline double lanczos_filter(double x) {
+    if (-3.0 <= x && x < 3.0) return sinc_filter(x) * sinc_filter(x / 3);
+    return 0.0;
+}
+
+static inline double filter_support(int filter) { return filter == MSPL_FILTER_LANCZOS ? 3.0 : 1.0; }
+
 }  // namespace mspl
 
 using namespace mspl;
 
-// Taps per output sample for a given size change (Resample.c precompute_coeffs: ksize).
-extern "C" int mspl_resample_ksize(int32_t in_size, int32_t out_size) {
+// Taps per output sample for a given size change and filter (Resample.c precompute_coeffs: ksize).
+extern "C" int mspl_resample_ksize_filter(int32_t in_size, int32_t out_size, int32_t filter) {
     if (in_size <= 0 || out_size <= 0) return MSPL_ERR_BAD_SHAPE;
+    if (filter != MSPL_FILTER_BILINEAR && filter != MSPL_FILTER_LANCZOS) return MSPL_ERR_UNSUPPORTED;
     double filterscale = (double)in_size / out_size;
     if (filterscale < 1.0) filterscale = 1.0;
-    return (int)ceil(1.0 * filterscale) * 2 + 1;
+    return (int)ceil(filter_support(filter) * filterscale) * 2 + 1;
 }
 
-// Host-side table builder: Pillow's precompute_coeffs + normalize_coeffs_8bpc for BILINEAR over the full box.
+extern "C" int mspl_resample_ksize(int32_t in_size, int32_t out_size) {
+    return mspl_resample_ksize_filter(in_size, out_size, MSPL_FILTER_BILINEAR);
+}
+
+// Host-side table builder: Pillow's precompute_coeffs + normalize_coeffs_8bpc for BILINEAR or LANCZOS over the full box.
 // bounds: (out,2) = (first source index, tap count); kk: (out, ksize) 22-bit fixed-point weights, zero padded.
-extern "C" int mspl_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk) {
+extern "C" int mspl_resample_coeffs_filter(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* kk) {
     MSPL_REQUIRE(bounds && kk, MSPL_ERR_NULL_POINTER, "resample_coeffs: null pointer");
     MSPL_REQUIRE(in_size > 0 && out_size > 0, MSPL_ERR_BAD_SHAPE, "resample_coeffs: bad sizes %d -> %d", in_size, out_size);
+    MSPL_REQUIRE(filter == MSPL_FILTER_BILINEAR || filter == MSPL_FILTER_LANCZOS, MSPL_ERR_UNSUPPORTED,
+                 "resample_coeffs: filter %d (1 = LANCZOS, 2 = BILINEAR)", filter);
     const double scale = (double)in_size / out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * filterscale;
+    const double support = filter_support(filter) * filterscale;
     const int ksize = (int)ceil(support) * 2 + 1;
     const double ss = 1.0 / filterscale;
     std::vector<double> w((size_t)ksize);
@@ -123,7 +144,8 @@ extern "C" int mspl_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* 
         xmax -= xmin;
         double ww = 0.0;
         for (int x = 0; x < xmax; ++x) {
-            w[x] = bilinear_filter((x + xmin - center + 0.5) * ss);
+            const double t = (x + xmin - center + 0.5) * ss;
+            w[x] = filter == MSPL_FILTER_LANCZOS ? lanczos_filter(t) : bilinear_filter(t);
             ww += w[x];
         }
         int32_t* k = kk + (size_t)xx * ksize;
@@ -136,6 +158,10 @@ extern "C" int mspl_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* 
         bounds[2 * xx + 1] = xmax;
     }
     return MSPL_OK;
+}
+
+extern "C" int mspl_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk) {
+    return mspl_resample_coeffs_filter(in_size, out_size, MSPL_FILTER_BILINEAR, bounds, kk);
 }
 
 // Source index per destination index for PIL NEAREST (Geometry.c ImagingScaleAffine: a running double sum).

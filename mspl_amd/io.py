@@ -14,15 +14,18 @@ launches with Pillow's exact fixed-point arithmetic; `LabelWriter` copies the me
 pinned memory and native worker threads (C++ + zlib inside the library) encode/write the PNGs while the next batch is on the GPU.  Decoding the source JPEG /
 PNG files stays with PIL on the host (file formats are outside the path).
 """
+import collections
 import ctypes
+import math
 import os
+import random
 import struct
 import zlib
 
 import numpy as np
 import torch
 
-from ._native import check, lib
+from ._native import FILTER_BILINEAR, FILTER_LANCZOS, TrainRec, check, lib
 
 def host_cores():
     """Cores this process may run on (the affinity mask where the platform has one: a container's share, not the machine)."""
@@ -169,6 +172,190 @@ class Preprocessor(object):
             if depth.shape[0] != N:
                 raise RuntimeError('mspl_amd: depth batch %d != image batch %d' % (depth.shape[0], N))
             d = self._bilinear(depth.unsqueeze(3), 1, None, None, flip)
+        return x, y, d
+
+
+# ------------------------------------------------------------------ device-side train augmentation
+TrainDraw = collections.namedtuple('TrainDraw', 'sw sh pad_w pad_h i j flip')
+TrainDraw.__doc__ = """One image's outcome of the train transforms' random draws: size after RandomScale (PIL order), RandomCrop's padding
+per side and origin (row i, column j) in the padded image, RandomFlip's mirror."""
+
+
+class TrainPreprocessor(object):
+    """`Compose([RandomScale(scale)?, RandomCrop(size, ignore_idx) if crop else Resize(size), RandomFlip(), Normalize() | Tensorize()])`
+    (transforms/segmentation/data_transforms.py:15-136,191-212) for a batch of decoded uint8 frames of one source size, on the device,
+    bit-identical to Pillow + torchvision.  size = (W, H) in PIL order.  The reference pipelines:
+
+        pipeline                                        scale        crop   ignore_idx
+        Greenhouse RGB-D (greenhouse.py:211-219, uest)  (0.5, 2.0)   no     --
+        CamVid (camvid.py:95-104)                       set          yes    4 or 12 (camvid.py:78-80)
+        Cityscapes (cityscapes.py:109-117)              set          yes    255
+        Greenhouse RGB (greenhouse.py:118-125)          None         yes    255
+
+    (CamVid's Resize after its RandomCrop is Pillow's copy path: the crop is the size.)  `draw()` makes the reference's random draws
+    with its own calls in its order; `__call__` uploads the per-image records (112 bytes each, pinned, asynchronous) and runs at most
+    three launches.  Label remaps that datasets apply before their transforms (camvid.py:120-125, greenhouse.py:248-251) and image
+    decoding stay with the caller."""
+
+    def __init__(self, size=(480, 256), scale=(0.5, 2.0), crop=False, ignore_idx=255, normalize=True, device='cuda'):
+        self.size = size if isinstance(size, tuple) else (size, size)
+        if scale is not None and not isinstance(scale, tuple):
+            scale = (scale, scale)                                  # RandomScale.__init__
+        self.scale = scale
+        self.crop = bool(crop)
+        self.ignore_idx = int(ignore_idx)
+        self.normalize = normalize
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('mspl_amd: TrainPreprocessor runs on the GPU (no CPU path)')
+        self._mean = self._std = None
+        self._tables = {}
+        self._ws = None
+        self._ws_dims = (0, 0, 0)
+
+    # ---- host: the reference's random draws
+    def draw(self, n, src_size, rng=random):
+        """Records of n images of source size src_size = (W, H), drawn like the reference's transforms draw them for one image after
+        the other: RandomScale one rng.random() (data_transforms.py:79-81), RandomCrop rng.randint(0, H'-th) then rng.randint(0, W'-tw)
+        unless the padded size is the crop (:105-113, :117-118), RandomFlip one rng.random() < 0.5 (:54)."""
+        w, h = src_size
+        tw, th = self.size
+        out = []
+        for _ in range(n):
+            sw, sh = w, h
+            if self.scale is not None:
+                lo, hi = self.scale
+                rand_log_scale = math.log(lo, 2) + rng.random() * (math.log(hi, 2) - math.log(lo, 2))
+                random_scale = math.pow(2, rand_log_scale)
+                sw, sh = int(round(w * random_scale)), int(round(h * random_scale))
+            pad_w = pad_h = i = j = 0
+            if self.crop:
+                pad_w = max(0, int((1 + tw - sw) / 2))
+                pad_h = max(0, int((1 + th - sh) / 2))
+                pw, ph = sw + 2 * pad_w, sh + 2 * pad_h
+                if not (pw == tw and ph == th):
+                    i = rng.randint(0, ph - th)
+                    j = rng.randint(0, pw - tw)
+            flip = rng.random() < 0.5
+            out.append(TrainDraw(sw, sh, pad_w, pad_h, i, j, flip))
+        return out
+
+    # ---- device tables, built once per (in, out, filter)
+    def _resample_table(self, n_in, n_out, filt):
+        key = (filt, n_in, n_out)
+        if key not in self._tables:
+            k = lib.mspl_resample_ksize_filter(n_in, n_out, filt)
+            if k <= 0:
+                check(k)
+            bounds = np.zeros((n_out, 2), np.int32)
+            kk = np.zeros((n_out, k), np.int32)
+            check(lib.mspl_resample_coeffs_filter(n_in, n_out, filt, bounds.ctypes.data, kk.ctypes.data))
+            t = np.concatenate([np.array([k + 2], np.int32), np.concatenate([bounds, kk], 1).ravel()])
+            self._tables[key] = torch.from_numpy(t).to(self.device)
+        return self._tables[key].data_ptr()
+
+    def _nearest_table(self, n_in, n_out):
+        key = ('n', n_in, n_out)
+        if key not in self._tables:
+            idx = np.zeros(n_out, np.int32)
+            check(lib.mspl_nearest_index(n_in, n_out, idx.ctypes.data))
+            self._tables[key] = torch.from_numpy(idx).to(self.device)
+        return self._tables[key].data_ptr()
+
+    def _record(self, p, Hs, Ws, with_label, with_depth):
+        W, H = self.size
+        r = TrainRec()
+        r.sh, r.sw, r.pad_h, r.pad_w, r.crop_i, r.crop_j, r.flip = p.sh, p.sw, p.pad_h, p.pad_w, p.i, p.j, int(bool(p.flip))
+        if p.sh <= 0 or p.sw <= 0:
+            raise RuntimeError('mspl_amd: TrainPreprocessor: scaled size %dx%d' % (p.sw, p.sh))
+        if p.sw != Ws:
+            r.scale_x = self._resample_table(Ws, p.sw, FILTER_LANCZOS)
+            r.dscale_x = self._resample_table(Ws, p.sw, FILTER_BILINEAR) if with_depth else None
+            r.near_x = self._nearest_table(Ws, p.sw) if with_label else None
+        if p.sh != Hs:
+            r.scale_y = self._resample_table(Hs, p.sh, FILTER_LANCZOS)
+            r.dscale_y = self._resample_table(Hs, p.sh, FILTER_BILINEAR) if with_depth else None
+            r.near_y = self._nearest_table(Hs, p.sh) if with_label else None
+        if not self.crop:
+            if p.sw != W:
+                r.out_x = self._resample_table(p.sw, W, FILTER_BILINEAR)
+                r.near_out_x = self._nearest_table(p.sw, W) if with_label else None
+            if p.sh != H:
+                r.out_y = self._resample_table(p.sh, H, FILTER_BILINEAR)
+                r.near_out_y = self._nearest_table(p.sh, H) if with_label else None
+        return r
+
+    def _up(self, t, name, ndim):
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(t)
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != ndim:
+            raise RuntimeError('mspl_amd: %s must be a uint8 tensor with %d dims, got %s %s'
+                               % (name, ndim, getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        return t.to(self.device, non_blocking=True).contiguous()
+
+    def _out(self, t, shape, dtype, name):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError('mspl_amd: TrainPreprocessor out= %s must be a contiguous CUDA %s tensor of shape %s, got %s %s'
+                               % (name, dtype, shape, t.dtype, tuple(t.shape)))
+        return t
+
+    def __call__(self, rgb, label=None, depth=None, params=None, out=None):
+        """rgb (N,Hs,Ws,3), label (N,Hs,Ws), depth (N,Hs,Ws): uint8, host or device.  params: N records from draw() (None: draw()
+        with the module-level `random`, as the reference's dataset does).  out: destination tensors -- the image tensor, or a tuple
+        (x, y, d) whose entries may be None -- e.g. a train step's static input buffers.  Returns (x (N,3,H,W) fp32, y (N,H,W) int64
+        | None, d (N,1,H,W) fp32 | None) on the device."""
+        rgb = self._up(rgb, 'rgb', 4)
+        if rgb.shape[3] != 3:
+            raise RuntimeError('mspl_amd: rgb must be (N,H,W,3) uint8, got %s' % (tuple(rgb.shape),))
+        N, Hs, Ws = rgb.shape[:3]
+        if label is not None:
+            label = self._up(label, 'label', 3)
+            if tuple(label.shape) != (N, Hs, Ws):
+                raise RuntimeError('mspl_amd: label shape %s does not match the image batch %s' % (tuple(label.shape), (N, Hs, Ws)))
+        if depth is not None:
+            depth = self._up(depth, 'depth', 3)
+            if tuple(depth.shape) != (N, Hs, Ws):
+                raise RuntimeError('mspl_amd: depth shape %s does not match the image batch %s' % (tuple(depth.shape), (N, Hs, Ws)))
+        if params is None:
+            params = self.draw(N, (Ws, Hs))
+        if len(params) != N:
+            raise RuntimeError('mspl_amd: %d records for a batch of %d images' % (len(params), N))
+        W, H = self.size
+        recs = (TrainRec * N)(*[self._record(p, Hs, Ws, label is not None, depth is not None) for p in params])
+        scaled = [(p.sh, p.sw) for p in params if (p.sh, p.sw) != (Hs, Ws)]
+        ws = None
+        if scaled:
+            need = (max([Hs] + [s[0] for s in scaled]), max([Ws] + [s[1] for s in scaled]))
+            if self.scale is not None:              # the whole range at once, so the workspace is allocated once
+                need = (max(need[0], int(math.ceil(Hs * self.scale[1])) + 1), max(need[1], int(math.ceil(Ws * self.scale[1])) + 1))
+            cn, ch, cw = self._ws_dims
+            if N > cn or need[0] > ch or need[1] > cw:
+                self._ws_dims = (max(N, cn), max(need[0], ch), max(need[1], cw))
+                nbytes = lib.mspl_train_transform_workspace_bytes(self._ws_dims[0], self._ws_dims[1], self._ws_dims[2], 1)
+                if nbytes < 0:
+                    check(int(nbytes))
+                self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+            ws = self._ws
+        max_sh, max_sw = (self._ws_dims[1], self._ws_dims[2]) if ws is not None else (max(p.sh for p in params), max(p.sw for p in params))
+        if isinstance(out, torch.Tensor):
+            out = (out, None, None)
+        ox, oy, od = out if out is not None else (None, None, None)
+        x = self._out(ox, (N, 3, H, W), torch.float32, 'x')
+        y = None if label is None else self._out(oy, (N, H, W), torch.int64, 'y')
+        d = None if depth is None else self._out(od, (N, 1, H, W), torch.float32, 'd')
+        if self.normalize and self._mean is None:
+            self._mean = torch.tensor(MEAN, dtype=torch.float32, device=self.device)
+            self._std = torch.tensor(STD, dtype=torch.float32, device=self.device)
+        host = torch.empty(ctypes.sizeof(recs), dtype=torch.uint8, pin_memory=True)
+        ctypes.memmove(host.data_ptr(), ctypes.addressof(recs), ctypes.sizeof(recs))
+        dev = host.to(self.device, non_blocking=True)              # the allocator keeps `host` until the copy has run
+        p = lambda t: None if t is None else t.data_ptr()
+        check(lib.mspl_train_transform_fwd(rgb.data_ptr(), p(label), p(depth), N, Hs, Ws, H, W, int(self.crop), self.ignore_idx,
+                                           ctypes.addressof(recs), dev.data_ptr(), p(self._mean if self.normalize else None),
+                                           p(self._std if self.normalize else None), p(ws), max_sh, max_sw, x.data_ptr(), p(y), p(d),
+                                           torch.cuda.current_stream(self.device).cuda_stream))
         return x, y, d
 
 
