@@ -171,6 +171,26 @@ int mspl_avgpool3x3s2_fwd(const float* x, int32_t N, int32_t C, int32_t H, int32
 int mspl_bilinear_fwd(const float* x, int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho,
                       int32_t Wo, int32_t align_corners, const mspl_epilogue_t* ep, float* out, void* stream);
 
+/* Head of a decoder stage in one launch (inference): the skip connection, the up-merge and the next pyramid block's projection,
+ *     proj = PReLU_p(BN_p(Wp . m)),  m = PReLU_b(BN_b(pw + bilinear_x2(bu))),  pw = gate * PReLU_e(BN_e(grouped3x3(enc))).
+ *     Replaces model/segmentation/espdnet_ue.py:276-299 (upsample, merge_enc_dec_lK, add, bu_br_lK), EfficientPWConv.forward's
+ *     expansion and scaling (nn_layers/efficient_pt.py:25-29; the gate itself comes from mspl_gap_gate_fwd / mspl_gate_from_sums_fwd)
+ *     and the projection_layer of the following EfficientPyrPool (nn_layers/efficient_pyramid_pool.py:20,38).
+ *     enc (N,Cin,H,W); bu (N,Cout,H/2,W/2), up-sampled with align_corners=True; w3 (Cout, Cin/groups, 3, 3) with groups =
+ *     gcd(Cin, Cout) (efficient_pt.py:19); e_* / b_* (Cout each) and p_* (P each): folded BatchNorm scale, shift and PReLU slope of
+ *     the expansion, of bu_br and of the projection; gate (N,Cout); wp (P,Cout); out (N,P,H,W).  Neither pw nor m is stored.  Per
+ *     `dec` channel the operations and their order are those of mspl_conv3x3_fwd, mspl_bilinear_fwd (pre_add) and the vector-unit
+ *     form of mspl_conv1x1_fwd, so the result equals that chain's up to the summation order of the projection.
+ *     Fused shapes: H, W even; P in {2, 6, 10, 16}; (Cin/groups, Cout/groups) in {(1,1), (8,3), (4,1) with groups >= 16 and
+ *     16 <= W <= 256, W % 4 == 0}; 16-byte-aligned tensors.  Anything else: MSPL_ERR_UNSUPPORTED, nothing is launched, and the caller runs the
+ *     three launches.
+ */
+int mspl_decoder_merge_fwd(const float* enc, const float* bu, const float* w3, const float* e_scale, const float* e_shift,
+                           const float* e_alpha, const float* gate, const float* b_scale, const float* b_shift,
+                           const float* b_alpha, const float* wp, const float* p_scale, const float* p_shift,
+                           const float* p_alpha, int32_t N, int32_t Cin, int32_t Cout, int32_t P, int32_t H, int32_t W,
+                           float* out, void* stream);
+
 /* adaptive_avg_pool2d (window [floor(i*I/O), ceil((i+1)*I/O)) ) + epilogue.
  *     Replaces efficient_pyramid_pool.py:46,52.
  */

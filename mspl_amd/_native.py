@@ -43,6 +43,7 @@ FILTER_LANCZOS = 1              # MSPL_FILTER_LANCZOS
 FILTER_BILINEAR = 2             # MSPL_FILTER_BILINEAR
 
 ABI_VERSION = 3                 # include/mspl_hip.h: mspl_abi_version()
+ERR_UNSUPPORTED = -2            # MSPL_ERR_UNSUPPORTED
 LAUNCH_THROUGHPUT = 1           # MSPL_LAUNCH_THROUGHPUT
 LAUNCH_K2_STREAM_OFF = 2        # MSPL_LAUNCH_K2_STREAM_OFF
 LAUNCH_K2_STREAM_FORCE = 4      # MSPL_LAUNCH_K2_STREAM_FORCE
@@ -68,6 +69,7 @@ SIGNATURES = {
                          ctypes.c_void_p],
     'mspl_avgpool3x3s2_fwd': [c_f32p, c_i32, c_i32, c_i32, c_i32, _EP, c_f32p, ctypes.c_void_p],
     'mspl_bilinear_fwd': [c_f32p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _EP, c_f32p, ctypes.c_void_p],
+    'mspl_decoder_merge_fwd': [c_f32p] * 14 + [c_i32] * 6 + [c_f32p, ctypes.c_void_p],
     'mspl_adaptive_avgpool_fwd': [c_f32p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _EP, c_f32p, ctypes.c_void_p],
     'mspl_avgpool3x3s2_psum_fwd': [c_f32p, c_i32, c_i32, c_i32, c_i32, _EP, c_f32p, c_f32p, ctypes.c_void_p],
     'mspl_avgpool3x3s2_psum_blocks': [c_i32, c_i32],

@@ -199,6 +199,7 @@ _EESP_DW_BN = os.environ.get('MSPL_EESP_DW_BN', '1') != '0'    # EESP in train()
 _CONV_SKIP = os.environ.get('MSPL_CONV_SKIP', '1') != '0'      # EESP in train(): projection + skip connection as one autograd node
 _FUSED_BN_TRAIN = os.environ.get('MSPL_FUSED_BN_TRAIN', '1') != '0'      # batch-statistics BN + PReLU as one autograd node
 _FUSED_DW_EXP = os.environ.get('MSPL_EESP_EXP', '1') != '0'   # inference: K2 + K3 of a stride-1 EESP block as one launch
+_FUSED_DEC_MERGE = True          # inference: skip 3x3 + up-merge + the next pyramid block's projection as one launch (ops.decoder_merge)
 _FUSED_NEXT_PROJ = os.environ.get('MSPL_EESP_NEXT', '1') != '0'   # ... and the following block's proj_1x1 inside that launch
 _FUSED_EESP_TRAIN = os.environ.get('MSPL_FUSED_EESP_TRAIN', '1') != '0'  # EESP block as one autograd node (frozen BatchNorm)
 _FUSED_PYR_TRAIN = os.environ.get('MSPL_FUSED_PYR_TRAIN', '1') != '0'    # pyramid body as one autograd node (frozen BatchNorm)
@@ -786,10 +787,12 @@ class EfficientPyrPool(nn.Module):
             return ag.conv_affine_prelu(out, conv.weight, 1, 1, None, conv.bias, None)
         return ag.affine_prelu(ag.conv(out, conv.weight, 1, 1), None, conv.bias, None)
 
-    def forward(self, x, fused=True):
+    def forward(self, x, fused=True, projected=False):
+        """projected=True (inference only): x is already projection_layer's output (decoder_stage_fused)."""
         if _training_path():
             return self._forward_train(x)
-        x = self.projection_layer(x)
+        if not projected:
+            x = self.projection_layer(x)
         height, width = x.shape[2:]
         sizes = self.branch_sizes(height, width)
         # a scale<1 branch whose clamped size exceeds the map (tiny maps) or a scale>1 branch are "up" for the kernel
@@ -815,15 +818,38 @@ class EfficientPWConv(nn.Module):
         if _training_path():
             gate = ag.gap_gate(x, self.wt_layer[1].weight)
             return ag.channel_scale(self.expansion_layer(x if _alias is None else _alias), gate)
+        return self.expand(x, self.gate(x))
+
+    def gate(self, x):
+        """wt_layer on the inference path: sigmoid(W . mean_hw(x)), (N, nout)."""
         sums = _recall_plane_sums(x)
         if sums is not None:
-            gate = ops.gate_from_sums(sums, self.wt_layer[1].weight, x.shape[2] * x.shape[3])
-        else:
-            gate = ops.gap_gate(x, self.wt_layer[1].weight)
+            return ops.gate_from_sums(sums, self.wt_layer[1].weight, x.shape[2] * x.shape[3])
+        return ops.gap_gate(x, self.wt_layer[1].weight)
+
+    def expand(self, x, gate):
         return ops.conv3x3(x, self.expansion_layer.cbr[0].weight, self.groups, ep=self.expansion_layer.epi(gate=gate))
 
     def __repr__(self):
         return '%s(in_channels=%d, out_channels=%d)' % (self.__class__.__name__, self.in_size, self.out_size)
+
+
+def decoder_stage_fusable(merge, enc, pyr):
+    """True when the head of a decoder stage (merge = its EfficientPWConv, enc = the encoder skip, pyr = the EfficientPyrPool that
+    follows) runs as one launch on the inference path."""
+    return (_FUSED_DEC_MERGE and not _training_path() and
+            ops.decoder_merge_shape_ok(merge.in_size, merge.out_size, pyr.proj_planes, enc.shape[2], enc.shape[3]))
+
+
+def decoder_stage_fused(merge, enc, gate, bu_lowres, br_seq, pyr):
+    """pyr.projection_layer(bu_br(merge(enc) + upsample2(bu))) in one launch (model/segmentation/espdnet_ue.py:276-299 up to the
+    projection of the pyramid block); None when the library does not take the shape."""
+    if tuple(enc.shape[2:]) != (bu_lowres.shape[2] * 2, bu_lowres.shape[3] * 2):
+        raise RuntimeError('The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 2'
+                           % (enc.shape[2], bu_lowres.shape[2] * 2))
+    exp, proj = merge.expansion_layer.cbr, pyr.projection_layer.cbr
+    return ops.decoder_merge(enc, bu_lowres, exp[0].weight, tuple(bn_fold(exp[1])) + (exp[2].weight,), gate,
+                             tuple(bn_fold(br_seq[0])) + (br_seq[1].weight,), proj[0].weight, tuple(bn_fold(proj[1])) + (proj[2].weight,))
 
 
 def decoder_merge(pw_out, bu_lowres, br_seq):

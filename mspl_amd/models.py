@@ -22,6 +22,7 @@ from torch.nn import init
 from . import ops
 from . import autograd as ag
 from .layers import (C, CBR, DownSampler, EESP, EfficientPWConv, EfficientPyrPool, ImagePyramid, _training_path, cached, run_eesp_chain,
+                     decoder_stage_fusable, decoder_stage_fused,
                      decoder_merge, fork, join, wait_mark)
 
 sc_ch_dict = {
@@ -206,6 +207,9 @@ class _SegBase(nn.Module):
         aux = None
         # the three skip connections depend on the encoder only, the auxiliary head on one decoder stage only: both
         # are issued on side streams (layers.fork / join) and overlap the main decoder chain
+        st2 = (self.merge_enc_dec_l2, self.bu_br_l2, self.bu_dec_l2)
+        st3 = (self.merge_enc_dec_l3, self.bu_br_l3, self.bu_dec_l3)
+        st4 = (self.merge_enc_dec_l4, self.bu_br_l4, self.bu_dec_l4)
         if isinstance(l1, tuple):                                # training path: (gate alias, 3x3 alias) pairs from _encode's fan_out
             pw2 = self.merge_enc_dec_l2(l3[0], _alias=l3[1])
             pw3 = self.merge_enc_dec_l3(l2[0], _alias=l2[1])
@@ -213,31 +217,44 @@ class _SegBase(nn.Module):
             e2 = e3 = e4 = None
             l1, l2, l3 = l1[0], l2[0], l3[0]
         else:
+          # inference: a stage whose head runs as one launch (layers.decoder_stage_fused: skip 3x3, up-merge and the pyramid
+          # block's projection) takes only the skip connection's GATE from the side stream, the others the whole skip connection
+          def skip(st, enc):
+              return st[0].gate(enc) if decoder_stage_fusable(st[0], enc, st[2]) else st[0](enc)
           with fork(1, (l1, l2, l3)) as f:
-            pw2 = self.merge_enc_dec_l2(l3);  e2 = f.mark()      # each skip connection is awaited on its own event:
-            pw3 = self.merge_enc_dec_l3(l2);  e3 = f.mark()      # stage k of the decoder starts when pw_k is ready, not
-            pw4 = self.merge_enc_dec_l4(l1);  e4 = f.mark()      # when the whole side stream has drained
+            pw2 = skip(st2, l3);  e2 = f.mark()                  # each skip connection is awaited on its own event:
+            pw3 = skip(st3, l2);  e3 = f.mark()                  # stage k of the decoder starts when pw_k is ready, not
+            pw4 = skip(st4, l1);  e4 = f.mark()                  # when the whole side stream has drained
         bu = self.bu_dec_l1(l4)
         if aux_layer == 0:
             with fork(2, (bu,)):
                 aux = self.aux_decoder(bu)
         wait_mark(e2, (pw2,))
-        bu = decoder_merge(pw2, bu, self.bu_br_l2)
-        bu = self.bu_dec_l2(bu)
+        bu = self._decode_stage(st2, l3, pw2, bu)
         if aux_layer == 1:
             with fork(2, (bu,)):
                 aux = self.aux_decoder(bu)
         wait_mark(e3, (pw3,))
-        bu = decoder_merge(pw3, bu, self.bu_br_l3)
-        bu = self.bu_dec_l3(bu)
+        bu = self._decode_stage(st3, l2, pw3, bu)
         if aux_layer == 2:
             with fork(2, (bu,)):
                 aux = self.aux_decoder(bu)
         wait_mark(e4, (pw4,))                                     # the side stream's last work: it is joined here
-        bu = decoder_merge(pw4, bu, self.bu_br_l4)
-        bu = self.bu_dec_l4(bu)
+        bu = self._decode_stage(st4, l1, pw4, bu)
         join(2, (aux,))
         return bu, aux
+
+    @staticmethod
+    def _decode_stage(st, enc, pw, bu):
+        """bu_dec_lK(bu_br_lK(merge_enc_dec_lK(enc) + upsample(bu))), espdnet_ue.py:276-299.  pw: the skip connection's output
+        (N, dec, H, W), or -- a 2-d (N, dec) tensor -- only its gate: the head of the stage then runs as one launch."""
+        merge, br, pyr = st
+        if pw.dim() == 2:
+            proj = decoder_stage_fused(merge, enc, pw, bu, br, pyr)
+            if proj is not None:
+                return pyr(proj, projected=True)
+            pw = merge.expand(enc, pw)                            # the library declined the shape after all
+        return pyr(decoder_merge(pw, bu, br))
 
     def get_basenet_params(self):
         return _param_gen([self.base_net])

@@ -5,6 +5,7 @@ checks device/dtype/contiguity on the host before a pointer reaches a kernel, al
 torch.empty, and launches on torch's current stream so the calls are capturable by torch.cuda.graph().
 """
 import ctypes
+import math
 
 import torch
 
@@ -302,6 +303,45 @@ def gate_from_sums(plane_sums, w, hw):
     gate = torch.empty((N, Cout), device=w.device, dtype=torch.float32)
     check(lib.mspl_gate_from_sums_fwd(_p(plane_sums), _p(w), N, Cin, Cout, nblk, int(hw), _p(gate), _stream()))
     return gate
+
+
+def decoder_merge_shape_ok(Cin, Cout, P, H, W):
+    """The shape rules of mspl_decoder_merge_fwd, for callers that plan their streams before the bottom-up tensor exists (the
+    library has the last word: decoder_merge returns None for what it does not take)."""
+    groups = math.gcd(Cin, Cout)
+    cg, cob = Cin // groups, Cout // groups
+    if H % 2 or W % 2 or H < 2 or W < 2 or P not in (2, 6, 10, 16) or Cout > 1024:
+        return False
+    return (cg, cob) in ((1, 1), (8, 3)) or ((cg, cob) == (4, 1) and groups >= 16 and W % 4 == 0 and 16 <= W <= 256 and H >= 4)
+
+
+def decoder_merge(enc, bu, w3, e_epi, gate, b_epi, wp, p_epi):
+    """Head of a decoder stage in one launch: PReLU(BN(wp . PReLU(BN(gate * PReLU(BN(grouped3x3(enc))) + upsample2(bu))))).
+    enc (N,Cin,H,W), bu (N,Cout,H/2,W/2), w3 (Cout,Cin/gcd,3,3), gate (N,Cout), wp (P,Cout[,1,1]); e_epi / b_epi / p_epi: (scale,
+    shift, alpha) of the expansion, of bu_br and of the projection.  Returns (N,P,H,W), or None when the shape is not a fused one
+    (mspl_decoder_merge_fwd: MSPL_ERR_UNSUPPORTED, nothing launched): the caller then runs conv3x3, bilinear and conv1x1."""
+    enc, bu, w3, wp = _f32(enc, 'enc'), _f32(bu, 'bu'), _f32(w3, 'w3'), _f32(wp, 'wp')
+    N, Cin, H, W = enc.shape
+    Cout, P = w3.shape[0], wp.shape[0]
+    if tuple(bu.shape) != (N, Cout, H // 2, W // 2) or H % 2 or W % 2:
+        return None
+    groups = math.gcd(Cin, Cout)
+    if tuple(w3.shape) != (Cout, Cin // groups, 3, 3) or wp.numel() != P * Cout:
+        raise RuntimeError('mspl_amd: decoder_merge weights %s / %s do not match Cin=%d Cout=%d'
+                           % (tuple(w3.shape), tuple(wp.shape), Cin, Cout))
+    gate = _vec(gate, N * Cout, 'gate')
+    es, eb, ea = [_vec(t, Cout, 'expansion epilogue') for t in e_epi]
+    bs, bb, ba = [_vec(t, Cout, 'bu_br epilogue') for t in b_epi]
+    ps, pb, pa = [_vec(t, P, 'projection epilogue') for t in p_epi]
+    if any(t is None for t in (es, eb, ea, bs, bb, ba, ps, pb, pa)):
+        return None
+    dst = torch.empty((N, P, H, W), device=enc.device, dtype=torch.float32)
+    rc = lib.mspl_decoder_merge_fwd(_p(enc), _p(bu), _p(w3), _p(es), _p(eb), _p(ea), _p(gate), _p(bs), _p(bb), _p(ba), _p(wp),
+                                    _p(ps), _p(pb), _p(pa), N, Cin, Cout, P, H, W, _p(dst), _stream())
+    if rc == nat.ERR_UNSUPPORTED:
+        return None
+    check(rc)
+    return dst
 
 
 def bilinear(x, size, ep=None, out=None, align_corners=True):
