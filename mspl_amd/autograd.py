@@ -15,6 +15,13 @@ from ._native import check, lib
 from .ops import Epi, _p, _stream
 
 
+# ---- switches (A/B aids; read once at import) ------------------------------------------------------------------------------
+_SMALL_BN = os.environ.get('MSPL_BN_SMALL', '1') != '0'               # small planes: one launch per BatchNorm node and direction
+_FUSED_EESP_BWD = os.environ.get('MSPL_FUSED_EESP_BWD', '1') != '0'   # stride-1 EESP blocks: the one-launch backward of K2
+_PYR_DOWN_FUSED = os.environ.get('MSPL_PYR_DOWN_FUSED', '1') != '0'   # low-resolution pyramid branches: one launch each way
+_GATE_EXPANDED = os.environ.get('MSPL_GATE_EXPANDED', '1') != '0'     # GapGateFn hands out its plane-constant gradient expanded
+
+
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
@@ -76,22 +83,97 @@ class WgradQueue(object):
 WGRADS = WgradQueue()
 
 
-def _wgrad_1x1_into_sink(gy, x, N, Cin, Cout, groups, H, W, sink, rowscale=None):
-    """gw of a grouped 1x1 convolution, accumulated into `sink`: queued inside grad_sinks(), launched at once otherwise.  rowscale: gy is
-    the gradient before a per-output-channel scale (applied at the store)."""
-    if (WGRADS.enabled and _SINKS[0]) or rowscale is not None:
-        WGRADS.add(gy, x, N, Cin, Cout, groups, H * W, sink, rowscale)
-        if not (WGRADS.enabled and _SINKS[0]):
-            WGRADS.flush()
-    else:
-        check(lib.mspl_conv_bwd_weight(_p(gy), _p(x), N, Cin, Cout, groups, H, W, 1, 1, 1, 1, _p(sink), _stream()))
-
-
 def _sink(p):
     if not _SINKS[0] or p is None or not p.requires_grad or not p.is_leaf:
         return None
     g = p.grad
     return g if (g is not None and g.is_contiguous() and g.dtype == torch.float32) else None
+
+
+# ---- where a parameter gradient goes -------------------------------------------------------------------------------------
+# Every node makes one of these per parameter (or group of parameters) in `forward` and keeps it on ctx.  In `backward` the
+# kernel writes to what buf() / bufs() hands out and the node returns result() / results() for that input.  That is all of
+# the bookkeeping: nothing else in this file looks at a sink.
+class GradDst(object):
+    """The destination of ONE parameter's gradient.  Made in `forward`: it captures the sink state of that moment (inside
+    `grad_sinks()`, a leaf that requires grad and has a contiguous float32 `.grad`: that buffer; anything else: no sink).
+
+      buf(zeroed)   the tensor the backward kernel writes to.  With a sink: the sink (the kernel adds to it).  Without: a fresh
+                    tensor of the parameter's shape, zero-filled when the kernel accumulates (zeroed=True), uninitialised when
+                    it overwrites.  Parameter None (gradient not wanted): None.
+      is_sink       for the kernels with an accumulate flag or a second, accumulating entry point.
+      result()      what `backward` returns for the parameter: None for a sink (the gradient is already in `.grad`) and for a
+                    parameter that is None, the tensor buf() made otherwise (autograd's AccumulateGrad adds it to `.grad`).
+
+    Example: d alpha of an EESP block's br_after_cat is the third member of `ctx.g_cat`: with the sinks on the kernel adds it to
+    br_after_cat.act.weight.grad and autograd gets None; with the sinks off it lands in row 2 of the group's zeroed (3, 4n)
+    accumulator and that row goes back to autograd."""
+
+    __slots__ = ('sink', 'spec', 'temp')
+
+    def __init__(self, p):
+        self.sink = _sink(p)
+        self.spec = None if (p is None or self.sink is not None) else (p.shape, p.device)      # of the tensor buf() has to make
+        self.temp = None
+
+    @property
+    def is_sink(self):
+        return self.sink is not None
+
+    def buf(self, zeroed):
+        if self.spec is None:
+            return self.sink
+        self.temp = (torch.zeros if zeroed else torch.empty)(self.spec[0], device=self.spec[1], dtype=torch.float32)
+        return self.temp
+
+    def result(self):
+        t, self.temp = self.temp, None
+        return t
+
+
+class GradDstGroup(object):
+    """GradDst for k parameters of ONE shape whose gradients one kernel accumulates (gamma | scale, beta | shift, alpha of a
+    BatchNorm + PReLU; the four depthwise branch weights of an EESP block).  bufs() makes ONE zero-filled (k,) + shape tensor
+    for all members that are wanted and have no sink (row i belongs to member i) and none at all when every such member has
+    a sink; results() is one result() per member."""
+
+    def __init__(self, *params):
+        self.members = [GradDst(p) for p in params]
+
+    def bufs(self):
+        need = [m for m in self.members if m.spec is not None]
+        if need:
+            shape, device = need[0].spec
+            acc = torch.zeros((len(self.members),) + tuple(shape), device=device, dtype=torch.float32)
+            for i, m in enumerate(self.members):
+                m.temp = acc[i] if m.spec is not None else None
+        return [m.temp if m.spec is not None else m.sink for m in self.members]
+
+    def ptrs(self):
+        """bufs() as the pointer array the four-branch kernels take."""
+        return (ctypes.c_void_p * len(self.members))(*[None if d is None else d.data_ptr() for d in self.bufs()])
+
+    def results(self):
+        return [m.result() for m in self.members]
+
+
+class GradDstPair(object):
+    """(d gamma, d beta) of the batch-statistics BatchNorm kernels.  They take one `direct` flag for both: add to the two sinks
+    when BOTH parameters have one, else overwrite two rows of the kernel's own output block, which then go back to autograd
+    (a lone sink is not used).  bufs(row_gamma, row_beta) -> (direct as 0 | 1, d gamma destination, d beta destination)."""
+
+    def __init__(self, gamma, beta):
+        self.gamma, self.beta = GradDst(gamma), GradDst(beta)
+        self.direct = self.gamma.is_sink and self.beta.is_sink
+
+    def bufs(self, row_gamma, row_beta):
+        if self.direct:
+            return 1, self.gamma.sink, self.beta.sink
+        self.gamma.temp, self.beta.temp = row_gamma, row_beta
+        return 0, row_gamma, row_beta
+
+    def results(self):
+        return self.gamma.result(), self.beta.result()
 
 
 # ---- transposed weights of the data-gradient convolutions, all in one launch ------------------------------------------------
@@ -200,13 +282,13 @@ class ConvFn(torch.autograd.Function):
         y = ops.conv1x1(x, w, groups) if k == 1 else ops.conv3x3(x, w, groups, stride)
         ctx.save_for_backward(x, w)
         ctx.cfg = (stride if k == 3 else 1, groups, k)
-        ctx.wsink = _sink(w)
+        ctx.g_w = GradDst(w)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gx, gw = _conv_backward(x, w, ctx.cfg, ctx.wsink, gy, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        gx, gw = _conv_backward(x, w, ctx.cfg, ctx.g_w, gy, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return gx, gw, None, None
 
 
@@ -221,29 +303,23 @@ class ConvSkipFn(torch.autograd.Function):
         x, w = _c(x), _c(w)
         ctx.save_for_backward(x, w)
         ctx.groups = groups
-        ctx.wsink = _sink(w)
+        ctx.g_w = GradDst(w)
         return ops.conv1x1(x, w, groups), x.view_as(x)
 
     @staticmethod
     def backward(ctx, gy, gskip):
         x, w = ctx.saved_tensors
         groups = ctx.groups
-        gx = gw = None
         if gy is None:
             return gskip, None, None
         gy = _c(gy)
+        gx = None
         if ctx.needs_input_grad[0]:
             wt = _transposed_weights(w, groups, 1)
             gx = ops.conv1x1(gy, wt, groups, None if gskip is None else Epi(residual=_c(gskip)))
         if ctx.needs_input_grad[1]:
-            N, Cin, H, W = x.shape
-            sink = ctx.wsink
-            gw = torch.empty_like(w) if sink is None else None
-            if sink is not None:
-                _wgrad_1x1_into_sink(gy, x, N, Cin, w.shape[0], groups, H, W, sink)
-            else:
-                check(lib.mspl_conv_bwd_weight(_p(gy), _p(x), N, Cin, w.shape[0], groups, H, W, 1, 1, 1, 0, _p(gw), _stream()))
-        return gx, gw, None
+            _conv_wgrad(gy, x, w.shape[0], (1, groups, 1), ctx.g_w)
+        return gx, ctx.g_w.result(), None
 
 
 def conv_skip(x, w, groups):
@@ -253,7 +329,8 @@ def conv_skip(x, w, groups):
 
 class EespDwBNFn(torch.autograd.Function):
     """K2 (the four dilated depthwise 3x3 + HFF + cat) and br_after_cat in train() of an EESP block as ONE node (the supervised
-    loop; the strided blocks and shapes the fused backward does not cover take mspl_hff_bn_stat_suffix_bwd + mspl_eesp_dw_bwd): forward = the K2 kernel + the BatchNorm node's forward (one launch on small planes); backward = the BatchNorm node's sums /
+    loop; the strided blocks and shapes the fused backward does not cover take mspl_hff_bn_stat_suffix_bwd + mspl_eesp_dw_bwd):
+    forward = the K2 kernel + the BatchNorm node's forward (one launch on small planes); backward = the BatchNorm node's sums /
     coefficients launch (mspl_bn_train_prelu_bwd without outputs) + mspl_eesp_bwd_fused_bnstat, which applies p z + q + the direct
     gradient, the HFF suffix sum and both gradients of the four branches from LDS: two launches where the node-per-op form ran the
     BatchNorm backward (1-2), the suffix sum, the data and the weight gradient, and wrote / re-read the 4n-channel gradient twice."""
@@ -263,42 +340,28 @@ class EespDwBNFn(torch.autograd.Function):
         x = _c(x)
         w4 = torch.stack([w.reshape(-1, 3, 3) for w in (w0, w1, w2, w3)]).contiguous()
         z = ops.eesp_dw_hff(x, w4, dil, stride)
-        N, C = z.shape[:2]
-        hw = z[0, 0].numel()
-        st = torch.empty(4, C, dtype=torch.float32, device=z.device)       # mean, invstd, scale, shift
-        gamma_c, beta_c, alpha_c = _c(gamma), _c(beta), _c(alpha)
-        if _SMALL_BN and lib.mspl_bn_train_small_fits(N, C, hw):
-            y = torch.empty_like(z)
-            check(lib.mspl_bn_train_small_fwd(_p(z), None, _p(gamma_c), _p(beta_c), _p(alpha_c), N, C, hw, eps, momentum, _p(running_mean),
-                                              _p(running_var), _p(nbt), _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]), _p(y), _stream()))
-        else:
-            check(lib.mspl_bn_batch_stats_fused_fwd(_p(z), N, C, hw, eps, momentum, _p(running_mean), _p(running_var), _p(gamma_c),
-                                                    _p(beta_c), _p(ws), _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]), _p(nbt), _stream()))
-            y = ops.pointwise(z, Epi(st[2], st[3], alpha_c))
+        gamma_c, alpha_c = _c(gamma), _c(alpha)
+        y, st, _ = _bn_train_forward(z, None, gamma_c, _c(beta), alpha_c, running_mean, running_var, eps, momentum, ws, nbt)
         ctx.save_for_backward(x, w4, z, st, gamma_c, alpha_c, ws)
-        ctx.cfg = (tuple(dil), w0.shape, stride)
-        ctx.sinks = ([_sink(w) for w in (w0, w1, w2, w3)], (_sink(gamma), _sink(beta), _sink(alpha)))
+        ctx.cfg = (tuple(dil), stride)
+        ctx.g_w4, ctx.g_bn, ctx.g_alpha = GradDstGroup(w0, w1, w2, w3), GradDstPair(gamma, beta), GradDst(alpha)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w4, z, st, gamma, alpha, ws = ctx.saved_tensors
-        dil, wshape, stride = ctx.cfg
-        wsinks, (s_g, s_b, s_a) = ctx.sinks
+        dil, stride = ctx.cfg
         gy = _c(gy)
         N, n, H, W = x.shape
         C = 4 * n
         dev = x.device
         # sums -> (d gamma, d beta, d alpha) and the statistics-path coefficients (p, q); no tensor is written
-        direct = s_g is not None and s_b is not None
         out = torch.empty(4, C, dtype=torch.float32, device=dev)
-        gal = s_a if s_a is not None else torch.zeros(C, device=dev)
+        direct, d_gamma, d_beta = ctx.g_bn.bufs(out[0], out[1])
         check(lib.mspl_bn_train_prelu_bwd(_p(z), None, _p(gy), _p(st[2]), _p(st[3]), _p(alpha), _p(gamma), _p(st[0]), _p(st[1]), N, C,
-                                          z.shape[2] * z.shape[3], None, None, _p(ws), 1 if direct else 0, _p(s_g if direct else out[0]),
-                                          _p(s_b if direct else out[1]), _p(gal), _p(out[2]), _p(out[3]), _stream()))
-        tmp = torch.zeros((4,) + tuple(wshape), device=dev, dtype=torch.float32) if any(t is None for t in wsinks) else None
-        dst = [wsinks[k] if wsinks[k] is not None else tmp[k] for k in range(4)]
-        ptrs = (ctypes.c_void_p * 4)(*[d.data_ptr() for d in dst])
+                                          z.shape[2] * z.shape[3], None, None, _p(ws), direct, _p(d_gamma), _p(d_beta),
+                                          _p(ctx.g_alpha.buf(zeroed=True)), _p(out[2]), _p(out[3]), _stream()))
+        ptrs = ctx.g_w4.ptrs()
         dil_c = (ctypes.c_int32 * 4)(*dil)
         gx = torch.empty_like(x)
         if stride == 1 and _FUSED_EESP_BWD and lib.mspl_eesp_bwd_fused_fits(N, n, H, W, dil_c):
@@ -312,9 +375,7 @@ class EespDwBNFn(torch.autograd.Function):
             check(lib.mspl_hff_bn_stat_suffix_bwd(_p(z), _p(gy), _p(st[2]), _p(st[3]), _p(alpha), _p(out[2]), _p(out[3]), N, n, Ho * Wo,
                                                   _p(gs), _stream()))
             check(lib.mspl_eesp_dw_bwd(_p(gs), _p(x), _p(w4), dil_c, stride, N, n, H, W, _p(gx), ptrs, _stream()))
-        gws = [None if wsinks[k] is not None else tmp[k] for k in range(4)]
-        return (gx, *gws, None, None, None if direct else out[0], None if direct else out[1], None if s_a is not None else gal,
-                None, None, None, None, None, None)
+        return (gx, *ctx.g_w4.results(), None, None, *ctx.g_bn.results(), ctx.g_alpha.result(), None, None, None, None, None, None)
 
 
 def eesp_dw_bn_fits(shape, dil):
@@ -325,20 +386,30 @@ def eesp_dw_bn_fits(shape, dil):
 
 def eesp_dw_bn(x, ws, dil, bn, alpha, stride=1):
     """PReLU(BatchNorm_train(K2(x))) for br_after_cat in train(): see EespDwBNFn."""
-    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-        raise RuntimeError('mspl_amd: BatchNorm2d variants without momentum / running statistics / affine parameters are '
-                           'not on the path (the reference uses the defaults everywhere)')
+    _require_default_bn(bn)
     return EespDwBNFn.apply(x, ws[0], ws[1], ws[2], ws[3], tuple(dil), int(stride), bn.weight, bn.bias, alpha, bn.running_mean, bn.running_var,
                             float(bn.eps), float(bn.momentum), _bn_workspace(bn, x.device), _bn_nbt(bn))
 
 
-def _conv_backward(x, w, cfg, sink, gy, need_gx, need_gw):
-    """(gx, gw) of a bias-free grouped convolution; gw is None when it was accumulated into `sink`."""
+def _conv_wgrad(gy, x, Cout, cfg, g_w):
+    """The weight gradient of a bias-free grouped convolution, to where `g_w` (a GradDst) says: added to the sink (a stride-1 1x1
+    inside grad_sinks(): queued, WgradQueue) or written to a fresh tensor."""
+    stride, groups, k = cfg
+    N, Cin, H, W = x.shape
+    d = g_w.buf(zeroed=False)
+    if g_w.is_sink and k == 1 and stride == 1 and WGRADS.enabled and _SINKS[0]:
+        WGRADS.add(gy, x, N, Cin, Cout, groups, H * W, d)
+    else:
+        check(lib.mspl_conv_bwd_weight(_p(gy), _p(x), N, Cin, Cout, groups, H, W, k, stride, 1, int(g_w.is_sink), _p(d), _stream()))
+
+
+def _conv_backward(x, w, cfg, g_w, gy, need_gx, need_gw):
+    """(gx, gw) of a bias-free grouped convolution; gw as `g_w` (a GradDst) hands it back."""
     stride, groups, k = cfg
     gy = _c(gy)
     N, Cin, H, W = x.shape
     Cout = w.shape[0]
-    gx = gw = None
+    gx = None
     if need_gx:
         if stride == 1:
             # the data gradient of a stride-1 convolution is a convolution with the transposed (and, for 3x3,
@@ -349,13 +420,8 @@ def _conv_backward(x, w, cfg, sink, gy, need_gx, need_gw):
             gx = torch.empty_like(x)
             check(lib.mspl_conv_bwd_data(_p(gy), _p(w), N, Cin, Cout, groups, H, W, k, stride, 1, 0, _p(gx), _stream()))
     if need_gw:
-        gw = torch.empty_like(w) if sink is None else None
-        if sink is not None and k == 1 and stride == 1:
-            _wgrad_1x1_into_sink(gy, x, N, Cin, Cout, groups, H, W, sink)
-        else:
-            check(lib.mspl_conv_bwd_weight(_p(gy), _p(x), N, Cin, Cout, groups, H, W, k, stride, 1, 0 if sink is None else 1,
-                                           _p(gw if sink is None else sink), _stream()))
-    return gx, gw
+        _conv_wgrad(gy, x, Cout, cfg, g_w)
+    return gx, g_w.result()
 
 
 class EespDwFn(torch.autograd.Function):
@@ -367,14 +433,14 @@ class EespDwFn(torch.autograd.Function):
         w4 = torch.stack([w.reshape(-1, 3, 3) for w in (w0, w1, w2, w3)]).contiguous()
         y = ops.eesp_dw_hff(x, w4, dil, stride)
         ctx.save_for_backward(x, w4)
-        ctx.cfg = (tuple(dil), stride, w0.shape)
-        ctx.wsinks = [_sink(w) for w in (w0, w1, w2, w3)]
+        ctx.cfg = (tuple(dil), stride)
+        ctx.g_w4 = GradDstGroup(w0, w1, w2, w3)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w4 = ctx.saved_tensors
-        dil, stride, wshape = ctx.cfg
+        dil, stride = ctx.cfg
         gy = _c(gy)
         N, n, H, W = x.shape
         Ho, Wo = gy.shape[2:]
@@ -382,14 +448,9 @@ class EespDwFn(torch.autograd.Function):
         check(lib.mspl_hff_suffix_sum(_p(gy), N, n, Ho * Wo, _p(gs), _stream()))
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         # all four branches in one data-gradient launch and one weight-gradient launch (eesp_dw_bwd.hip)
-        sinks = ctx.wsinks
-        tmp = torch.zeros((4,) + tuple(wshape), device=x.device, dtype=torch.float32) if any(s_ is None for s_ in sinks) else None
-        dst = [sinks[k] if sinks[k] is not None else tmp[k] for k in range(4)]
-        ptrs = (ctypes.c_void_p * 4)(*[d.data_ptr() for d in dst])
         dil_c = (ctypes.c_int32 * 4)(*dil)
-        check(lib.mspl_eesp_dw_bwd(_p(gs), _p(x), _p(w4), dil_c, stride, N, n, H, W, _p(gx), ptrs, _stream()))
-        gws = [None if sinks[k] is not None else tmp[k] for k in range(4)]
-        return (gx, *gws, None, None)
+        check(lib.mspl_eesp_dw_bwd(_p(gs), _p(x), _p(w4), dil_c, stride, N, n, H, W, _p(gx), ctx.g_w4.ptrs(), _stream()))
+        return (gx, *ctx.g_w4.results(), None, None)
 
 
 class AffinePReLUFn(torch.autograd.Function):
@@ -408,42 +469,35 @@ class AffinePReLUFn(torch.autograd.Function):
         y = ops.pointwise(c, Epi(scale, shift, alpha, pre_add=pre_add, residual=residual))
         ctx.save_for_backward(c, scale, shift, alpha, pre_add, residual, mean, inv)
         ctx.bn = gamma is not None
-        ctx.sinks = (_sink(gamma if ctx.bn else scale), _sink(beta if ctx.bn else shift), _sink(alpha))
+        ctx.g_aff = GradDstGroup(gamma if ctx.bn else scale, beta if ctx.bn else shift, alpha)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         c, scale, shift, alpha, pre_add, residual, mean, inv = ctx.saved_tensors
-        gc, gz, r_sc, r_sh, r_al = _affine_backward(c, scale, shift, alpha, pre_add, residual, mean, inv, ctx.bn, ctx.sinks, gy)
+        gc, gz, r_sc, r_sh, r_al = _affine_backward(c, scale, shift, alpha, pre_add, residual, mean, inv, ctx.bn, ctx.g_aff, gy)
         gpre = gc if pre_add is not None else None
         if ctx.bn:
             return gc, None, None, r_al, gpre, gz, r_sc, r_sh, None, None
         return gc, r_sc, r_sh, r_al, gpre, gz, None, None, None, None
 
 
-def _affine_backward(c, scale, shift, alpha, pre_add, residual, mean, inv, bn, sinks, gy):
-    """Backward of y = PReLU((c + pre_add) * scale + shift + residual): (gc, gz = d residual, and the per-channel gradients that
-    were NOT accumulated into a sink: d scale | d gamma, d shift | d beta, d alpha)."""
+def _affine_backward(c, scale, shift, alpha, pre_add, residual, mean, inv, bn, g_aff, gy):
+    """Backward of y = PReLU((c + pre_add) * scale + shift + residual): (gc, gz = d residual, and what `g_aff`, the GradDstGroup of
+    (scale | gamma, shift | beta, alpha), hands back for the three per-channel gradients)."""
     gy = _c(gy)
     N, C = c.shape[:2]
     hw = c[0, 0].numel()
-    dev = c.device
     gz = torch.empty_like(c) if residual is not None else None
     gc = torch.empty_like(c)
-    s_sc, s_sh, s_al = sinks
-    # (a zeroed accumulator only for a gradient that is wanted and has no sink)
-    need = (scale is not None and s_sc is None) or (shift is not None and s_sh is None) or (alpha is not None and s_al is None)
-    gacc = torch.zeros(3, C, device=dev) if need else None
-    gsc = (s_sc if s_sc is not None else gacc[0]) if scale is not None else None
-    gsh = (s_sh if s_sh is not None else gacc[1]) if shift is not None else None
-    gal = (s_al if s_al is not None else gacc[2]) if alpha is not None else None
+    gsc, gsh, gal = g_aff.bufs()
     if bn:
         check(lib.mspl_bn_prelu_bwd(_p(c), _p(pre_add), _p(residual), _p(gy), _p(scale), _p(shift), _p(alpha), _p(mean), _p(inv),
                                     N, C, hw, _p(gz), _p(gc), _p(gsc), _p(gsh), _p(gal), _stream()))
     else:
         check(lib.mspl_affine_prelu_bwd(_p(c), _p(pre_add), _p(residual), _p(gy), _p(scale), _p(shift), _p(alpha), N, C, hw,
                                         _p(gz), _p(gc), _p(gsc), _p(gsh), _p(gal), _stream()))
-    return gc, gz, (gsc if s_sc is None else None), (gsh if s_sh is None else None), (gal if s_al is None else None)
+    return (gc, gz, *g_aff.results())
 
 
 class ConvAffinePReLUFn(torch.autograd.Function):
@@ -466,16 +520,16 @@ class ConvAffinePReLUFn(torch.autograd.Function):
         y = ops.conv1x1(x, w, groups, ep) if k == 1 else ops.conv3x3(x, w, groups, stride, 0, ep)
         ctx.save_for_backward(x, w, c, scale, shift, alpha, pre_add, residual, mean, inv)
         ctx.cfg = (s, groups, k)
-        ctx.wsink = _sink(w)
+        ctx.g_w = GradDst(w)
         ctx.bn = gamma is not None
-        ctx.sinks = (_sink(gamma if ctx.bn else scale), _sink(beta if ctx.bn else shift), _sink(alpha))
+        ctx.g_aff = GradDstGroup(gamma if ctx.bn else scale, beta if ctx.bn else shift, alpha)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w, c, scale, shift, alpha, pre_add, residual, mean, inv = ctx.saved_tensors
-        gc, gz, r_sc, r_sh, r_al = _affine_backward(c, scale, shift, alpha, pre_add, residual, mean, inv, ctx.bn, ctx.sinks, gy)
-        gx, gw = _conv_backward(x, w, ctx.cfg, ctx.wsink, gc, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        gc, gz, r_sc, r_sh, r_al = _affine_backward(c, scale, shift, alpha, pre_add, residual, mean, inv, ctx.bn, ctx.g_aff, gy)
+        gx, gw = _conv_backward(x, w, ctx.cfg, ctx.g_w, gc, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         gpre = gc if pre_add is not None else None
         if ctx.bn:
             return gx, gw, None, None, None, None, r_al, gpre, gz, r_sc, r_sh, None, None
@@ -522,9 +576,6 @@ class FanOutFn(torch.autograd.Function):
         return out, None
 
 
-_FUSED_EESP_BWD = os.environ.get('MSPL_FUSED_EESP_BWD', '1') != '0'
-
-
 def _stack4(ws):
     """(4, n, 3, 3) tensor of the four depthwise branch weights: a VIEW when they sit back to back in one storage (the flat
     parameter buffer of FlatAdam / FlatSGD lays consecutive parameters out contiguously), else a torch.stack copy."""
@@ -567,15 +618,15 @@ class EESPFn(torch.autograd.Function):
         ctx.save_for_backward(x, c1, o1, z2, y2, c3, w4, wp, we, ap, a2, am, fp['scale'], fp['shift'], fp['mean'], fp['inv'],
                               fb['scale'], fb['shift'], fb['mean'], fb['inv'], fe['scale'], fe['shift'], fe['mean'], fe['inv'])
         ctx.cfg = cfg
-        ctx.wshape = tuple(w0.shape)
-        ctx.sinks = {'wp': _sink(wp), 'p': (_sink(gp), _sink(bp), _sink(ap)), 'w4': [_sink(t) for t in (w0, w1, w2, w3)],
-                     'b': (_sink(g2), _sink(b2), _sink(a2)), 'we': _sink(we), 'e': (_sink(ge), _sink(be), _sink(am))}
+        ctx.g_wp, ctx.g_proj = GradDst(wp), GradDstGroup(gp, bp, ap)              # proj_1x1: weight; (gamma, beta, alpha)
+        ctx.g_w4, ctx.g_cat = GradDstGroup(w0, w1, w2, w3), GradDstGroup(g2, b2, a2)   # the four branches; br_after_cat
+        ctx.g_we, ctx.g_exp = GradDst(we), GradDstGroup(ge, be, am)              # conv_1x1_exp (+ module_act)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         (x, c1, o1, z2, y2, c3, w4, wp, we, ap, a2, am, sp, hp, mp, ip, sb, hb, mb, ib, se, he, me, ie) = ctx.saved_tensors
-        cfg, sk = ctx.cfg, ctx.sinks
+        cfg = ctx.cfg
         stride, dil, groups, residual = cfg['stride'], cfg['dil'], cfg['groups'], cfg['residual']
         gy = _c(gy)
         N, Cin, H, W = x.shape
@@ -583,35 +634,22 @@ class EESPFn(torch.autograd.Function):
         Ho, Wo = z2.shape[2:]
         dev = x.device
         # conv_1x1_exp's BatchNorm (+ residual, module_act) and the convolution itself
-        gc3, gres, r_ge, r_be, r_am = _affine_backward(c3, se, he, am, None, x if residual else None, me, ie, True, sk['e'], gy)
-        gy2, gwe = _conv_backward(y2, we, (1, groups, 1), sk['we'], gc3, True, True)
+        gc3, gres, r_ge, r_be, r_am = _affine_backward(c3, se, he, am, None, x if residual else None, me, ie, True, ctx.g_exp, gy)
+        gy2, gwe = _conv_backward(y2, we, (1, groups, 1), ctx.g_we, gc3, True, True)
         # br_after_cat backward + HFF suffix sum
-        C4 = 4 * n
-        s_g2, s_b2, s_a2 = sk['b']
-        acc = torch.zeros(3, C4, device=dev) if (s_g2 is None or s_b2 is None or s_a2 is None) else None
-        d_g2 = s_g2 if s_g2 is not None else acc[0]
-        d_b2 = s_b2 if s_b2 is not None else acc[1]
-        d_a2 = s_a2 if s_a2 is not None else acc[2]
+        d_g2, d_b2, d_a2 = ctx.g_cat.bufs()
         go1 = torch.empty_like(o1)
-        wsinks = sk['w4']
-        tmp = torch.zeros((4,) + ctx.wshape, device=dev, dtype=torch.float32) if any(t is None for t in wsinks) else None
-        dst = [wsinks[k] if wsinks[k] is not None else tmp[k] for k in range(4)]
-        ptrs = (ctypes.c_void_p * 4)(*[d.data_ptr() for d in dst])
+        ptrs = ctx.g_w4.ptrs()
         dil_c = (ctypes.c_int32 * 4)(*dil)
-        r_gp = r_bp = r_ap = None
         if stride == 1 and _FUSED_EESP_BWD and lib.mspl_eesp_bwd_fused_fits(N, n, H, W, dil_c):
             # one launch: BatchNorm/PReLU backward + suffix sum + both gradients of the four branches (no suffix-summed tensor in
             # memory) + proj_1x1's BatchNorm/PReLU backward on the way out: what is written is dL/d(projection's convolution result)
-            s_gp, s_bp, s_ap = sk['p']
-            pacc = torch.zeros(3, n, device=dev) if (s_gp is None or s_bp is None or s_ap is None) else None
-            d_gp = s_gp if s_gp is not None else pacc[0]
-            d_bp = s_bp if s_bp is not None else pacc[1]
-            d_ap = s_ap if s_ap is not None else pacc[2]
+            d_gp, d_bp, d_ap = ctx.g_proj.bufs()
             gc1 = go1
             check(lib.mspl_eesp_bwd_fused(_p(z2), _p(gy2), _p(o1), _p(w4), dil_c, _p(sb), _p(hb), _p(a2), _p(mb), _p(ib), N, n, H, W,
                                           _p(gc1), ptrs, _p(d_g2), _p(d_b2), _p(d_a2), _p(c1), _p(sp), _p(hp), _p(ap), _p(mp), _p(ip),
                                           _p(d_gp), _p(d_bp), _p(d_ap), _stream()))
-            r_gp, r_bp, r_ap = (None if s_gp is not None else d_gp), (None if s_bp is not None else d_bp), (None if s_ap is not None else d_ap)
+            r_gp, r_bp, r_ap = ctx.g_proj.results()
         else:
             gs = torch.empty((4, N, n, Ho, Wo), device=dev, dtype=torch.float32)
             check(lib.mspl_hff_bn_prelu_suffix_bwd(_p(z2), _p(gy2), _p(sb), _p(hb), _p(a2), _p(mb), _p(ib), N, n, Ho * Wo, _p(gs),
@@ -619,25 +657,15 @@ class EESPFn(torch.autograd.Function):
             # the four depthwise branches
             check(lib.mspl_eesp_dw_bwd(_p(gs), _p(o1), _p(w4), dil_c, stride, N, n, H, W, _p(go1), ptrs, _stream()))
             # proj_1x1's BatchNorm + PReLU
-            gc1, _, r_gp, r_bp, r_ap = _affine_backward(c1, sp, hp, ap, None, None, mp, ip, True, sk['p'], go1)
+            gc1, _, r_gp, r_bp, r_ap = _affine_backward(c1, sp, hp, ap, None, None, mp, ip, True, ctx.g_proj, go1)
         # proj_1x1's convolution; the residual link's gradient rides on the data gradient's epilogue
-        gx = gwp = None
+        gx = None
         if ctx.needs_input_grad[0]:
             wt = _transposed_weights(wp, groups, 1)
             gx = ops.conv1x1(gc1, wt, groups, Epi(residual=gres) if gres is not None else None)
-        s_wp = sk['wp']
-        gwp = torch.empty_like(wp) if s_wp is None else None
-        if s_wp is not None:
-            _wgrad_1x1_into_sink(gc1, x, N, Cin, n, groups, H, W, s_wp)
-        else:
-            check(lib.mspl_conv_bwd_weight(_p(gc1), _p(x), N, Cin, n, groups, H, W, 1, 1, 1, 0, _p(gwp), _stream()))
-        ret = lambda sink, t: None if sink is not None else t          # noqa: E731
-        gws = [ret(wsinks[k], tmp[k] if tmp is not None else None) for k in range(4)]
-        return (gx, None, None, None, None, gwp, r_gp, r_bp, r_ap, *gws, ret(s_g2, d_g2), ret(s_b2, d_b2), ret(s_a2, d_a2),
-                gwe, r_ge, r_be, r_am if am is not None else None)
-
-
-_PYR_DOWN_FUSED = os.environ.get('MSPL_PYR_DOWN_FUSED', '1') != '0'   # low-resolution pyramid branches: one launch each way (A/B aid)
+        _conv_wgrad(gc1, x, n, (1, groups, 1), ctx.g_wp)
+        return (gx, None, None, None, None, ctx.g_wp.result(), r_gp, r_bp, r_ap, *ctx.g_w4.results(), *ctx.g_cat.results(),
+                gwe, r_ge, r_be, r_am)
 
 
 def _pyr_down_forward(x, sizes, stage_ws, down):
@@ -694,6 +722,52 @@ def _pyr_down_backward(gt, x_shape, sizes, stage_ws, pooled, down, g_stage):
     return adds
 
 
+def _pyr_forward_tables(x, sizes, stage_ws):
+    """What both pyramid nodes hand to mspl_pyrpool_fused_train_fwd: (sizes as int tuples, down = the indices of the scale < 1 branches,
+    their pooled maps for the backward, the (hs, ws, sw, de) tables -- branch heights / widths, the stage weight of a scale >= 1 branch,
+    the convolved map of a scale < 1 branch --, the tensors those pointers need alive until the launch)."""
+    N, P, h, w = x.shape
+    sizes = [tuple(int(v) for v in s_) for s_ in sizes]
+    nb = len(sizes)
+    down = [i for i, (hs_, ws_) in enumerate(sizes) if (hs_ < h or ws_ < w)]
+    pooled, down_es = _pyr_down_forward(x, sizes, stage_ws, down)
+    hs = (ctypes.c_int32 * nb)(*[s_[0] for s_ in sizes])
+    ws = (ctypes.c_int32 * nb)(*[s_[1] for s_ in sizes])
+    sw, de = (ctypes.c_void_p * nb)(), (ctypes.c_void_p * nb)()
+    keep = [down_es]
+    for i in range(nb):
+        if i in down:
+            de[i] = down_es[i].data_ptr()
+        else:
+            t = _c(stage_ws[i])
+            keep.append(t)
+            sw[i] = t.data_ptr()
+    return sizes, down, pooled, (hs, ws, sw, de), keep
+
+
+def _pyr_branch_backward(x, gt, sizes, down, saved, g_stage):
+    """The branches' backward of both pyramid nodes: gt (nb,N,P,h,w) = dL/d(branch value), saved = the tail of the node's saved tensors
+    (*stage_ws, *pooled maps of `down`), g_stage = the GradDst of every stage weight -> (gx, what autograd gets for the stage weights)."""
+    N, P, h, w = x.shape
+    stage_ws, pooled = saved[:len(sizes)], dict(zip(down, saved[len(sizes):]))
+    d_stage = [g.buf(zeroed=True) for g in g_stage]
+    # scale < 1 branches (small maps): bilinear^T -> depthwise 3x3 backward -> adaptive pool^T, existing kernels
+    adds = _pyr_down_backward(gt, (N, P, h, w), sizes, stage_ws, pooled, down, d_stage)
+    # scale >= 1 branches (up to three, pyr_body_fits) in one launch, the low-resolution contributions (up to two) added in.
+    # (always launched: the stage weights' gradients come from it)
+    up = [i for i in range(len(sizes)) if i not in down]
+    nbp = len(up)
+    hsa = (ctypes.c_int32 * nbp)(*[sizes[i][0] for i in up])
+    wsa = (ctypes.c_int32 * nbp)(*[sizes[i][1] for i in up])
+    swp = (ctypes.c_void_p * nbp)(*[stage_ws[i].data_ptr() for i in up])
+    gtp = (ctypes.c_void_p * nbp)(*[gt[i].data_ptr() for i in up])
+    gwp = (ctypes.c_void_p * nbp)(*[d_stage[i].data_ptr() for i in up])
+    gx = torch.empty_like(x)
+    check(lib.mspl_pyrpool_branch_bwd(_p(x), N, P, h, w, nbp, hsa, wsa, swp, gtp, gwp, _p(adds[0] if adds else None),
+                                      _p(adds[1] if len(adds) > 1 else None), _p(gx), _stream()))
+    return gx, [g.result() for g in g_stage]
+
+
 class PyrBodyFn(torch.autograd.Function):
     """The EfficientPyrPool body between projection_layer and the last 1x1 (nn_layers/efficient_pyramid_pool.py:39-58: the five
     branches, merge_layer.0 BatchNorm + PReLU over the concatenation, Shuffle, merge_layer.2 grouped 3x3 + BatchNorm + PReLU) as ONE
@@ -714,19 +788,7 @@ class PyrBodyFn(torch.autograd.Function):
         nb = len(sizes)
         br_scale, br_shift = bn0['scale'], bn0['shift']
         m_scale, m_shift = bn2['scale'], bn2['shift']
-        down = [i for i, (hs_, ws_) in enumerate(sizes) if (hs_ < h or ws_ < w)]
-        pooled, down_es = _pyr_down_forward(x, sizes, stage_ws, down)
-        hs = (ctypes.c_int32 * nb)(*[int(s_[0]) for s_ in sizes])
-        ws = (ctypes.c_int32 * nb)(*[int(s_[1]) for s_ in sizes])
-        sw, de = (ctypes.c_void_p * nb)(), (ctypes.c_void_p * nb)()
-        keep = []
-        for i in range(nb):
-            if i in down:
-                de[i] = down_es[i].data_ptr()
-            else:
-                t = _c(stage_ws[i])
-                keep.append(t)
-                sw[i] = t.data_ptr()
+        sizes, down, pooled, (hs, ws, sw, de), keep = _pyr_forward_tables(x, sizes, stage_ws)
         merge_w = _c(merge_w)
         y = torch.empty((N, P, h, w), device=x.device, dtype=torch.float32)
         mraw = torch.empty_like(y)
@@ -736,9 +798,9 @@ class PyrBodyFn(torch.autograd.Function):
                                                _p(merge_w), ctypes.byref(ep), _p(y), _p(zcat), _stream()))
         ctx.save_for_backward(x, zcat, mraw, br_scale, br_shift, br_alpha, merge_w, m_scale, m_shift, m_alpha,
                               bn0['mean'], bn0['inv'], bn2['mean'], bn2['inv'], *stage_ws, *[pooled[i] for i in down])
-        ctx.sizes, ctx.down = [tuple(int(v) for v in s_) for s_ in sizes], down
-        ctx.sinks = ([_sink(t) for t in (br_gamma, br_beta, br_alpha, merge_w, m_gamma, m_beta, m_alpha)],
-                     [_sink(t) for t in stage_ws])
+        ctx.sizes, ctx.down = sizes, down
+        ctx.g_par = [GradDst(t) for t in (br_gamma, br_beta, br_alpha, merge_w, m_gamma, m_beta, m_alpha)]
+        ctx.g_stage = [GradDst(t) for t in stage_ws]
         return y
 
     @staticmethod
@@ -747,44 +809,16 @@ class PyrBodyFn(torch.autograd.Function):
         x, zcat, mraw, br_scale, br_shift, br_alpha, merge_w, m_scale, m_shift, m_alpha, mean0, inv0, mean2, inv2 = sv[:14]
         sizes, down = ctx.sizes, ctx.down
         nb = len(sizes)
-        stage_ws = sv[14:14 + nb]
-        pooled = dict(zip(down, sv[14 + nb:]))
         gy = _c(gy)
         N, P, h, w = x.shape
-        dev = x.device
-        psinks, wsinks = ctx.sinks
-
-        def dst(sink, shape):
-            return sink if sink is not None else torch.zeros(shape, device=dev, dtype=torch.float32)
-        g_br_gamma, g_br_beta, g_br_alpha = dst(psinks[0], (nb * P,)), dst(psinks[1], (nb * P,)), dst(psinks[2], (nb * P,))
-        g_merge_w = dst(psinks[3], tuple(merge_w.shape))
-        g_m_gamma, g_m_beta = dst(psinks[4], (P,)), dst(psinks[5], (P,))
-        g_m_alpha = dst(psinks[6], (P,)) if m_alpha is not None else None
-        gt = torch.empty((nb, N, P, h, w), device=dev, dtype=torch.float32)
+        # d (br_gamma, br_beta, br_alpha, merge_w, m_gamma, m_beta, m_alpha), each accumulated by the kernel (m_alpha may be None)
+        d_par = [g.buf(zeroed=True) for g in ctx.g_par]
+        gt = torch.empty((nb, N, P, h, w), device=x.device, dtype=torch.float32)
         check(lib.mspl_pyrpool_merge_bwd(_p(gy), _p(mraw), _p(zcat), N, P, h, w, nb, _p(br_scale), _p(br_shift), _p(br_alpha),
                                          _p(mean0), _p(inv0), _p(merge_w), _p(m_scale), _p(m_shift), _p(m_alpha), _p(mean2),
-                                         _p(inv2), _p(gt), _p(g_br_gamma), _p(g_br_beta), _p(g_br_alpha), _p(g_merge_w),
-                                         _p(g_m_gamma), _p(g_m_beta), _p(g_m_alpha), _stream()))
-        g_stage = [dst(wsinks[i], tuple(stage_ws[i].shape)) for i in range(nb)]
-        # scale < 1 branches (small maps): bilinear^T -> depthwise 3x3 backward -> adaptive pool^T, existing kernels
-        adds = _pyr_down_backward(gt, (N, P, h, w), sizes, stage_ws, pooled, down, g_stage)
-        # scale >= 1 branches (up to three, pyr_body_fits) in one launch, the low-resolution contributions (up to two) added in.
-        # (always launched: the stage weights' gradients come from it)
-        up = [i for i in range(nb) if i not in down]
-        nbp = len(up)
-        hsa = (ctypes.c_int32 * nbp)(*[sizes[i][0] for i in up])
-        wsa = (ctypes.c_int32 * nbp)(*[sizes[i][1] for i in up])
-        swp = (ctypes.c_void_p * nbp)(*[stage_ws[i].data_ptr() for i in up])
-        gtp = (ctypes.c_void_p * nbp)(*[gt[i].data_ptr() for i in up])
-        gwp = (ctypes.c_void_p * nbp)(*[g_stage[i].data_ptr() for i in up])
-        gx = torch.empty_like(x)
-        check(lib.mspl_pyrpool_branch_bwd(_p(x), N, P, h, w, nbp, hsa, wsa, swp, gtp, gwp, _p(adds[0] if adds else None),
-                                          _p(adds[1] if len(adds) > 1 else None), _p(gx), _stream()))
-        ret = lambda sink, t: None if sink is not None else t          # noqa: E731
-        return (gx, None, None, None, ret(psinks[0], g_br_gamma), ret(psinks[1], g_br_beta), ret(psinks[2], g_br_alpha),
-                ret(psinks[3], g_merge_w), ret(psinks[4], g_m_gamma), ret(psinks[5], g_m_beta),
-                None if m_alpha is None else ret(psinks[6], g_m_alpha),
-                *[ret(wsinks[i], g_stage[i]) for i in range(nb)])
+                                         _p(inv2), _p(gt), *[_p(d) for d in d_par], _stream()))
+        gx, g_stage_ws = _pyr_branch_backward(x, gt, sizes, down, sv[14:], ctx.g_stage)
+        return (gx, None, None, None, *[g.result() for g in ctx.g_par], *g_stage_ws)
 
 
 _CONST_VECS = {}
@@ -816,19 +850,7 @@ class PyrBodyBNFn(torch.autograd.Function):
         N, P, h, w = x.shape
         nb = len(sizes)
         dev = x.device
-        down = [i for i, (hs_, ws_) in enumerate(sizes) if (hs_ < h or ws_ < w)]
-        pooled, down_es = _pyr_down_forward(x, sizes, stage_ws, down)
-        hs = (ctypes.c_int32 * nb)(*[int(s_[0]) for s_ in sizes])
-        ws = (ctypes.c_int32 * nb)(*[int(s_[1]) for s_ in sizes])
-        sw, de = (ctypes.c_void_p * nb)(), (ctypes.c_void_p * nb)()
-        keep = []
-        for i in range(nb):
-            if i in down:
-                de[i] = down_es[i].data_ptr()
-            else:
-                t = _c(stage_ws[i])
-                keep.append(t)
-                sw[i] = t.data_ptr()
+        sizes, down, pooled, (hs, ws, sw, de), keep = _pyr_forward_tables(x, sizes, stage_ws)
         merge_w = _c(merge_w)
         br_alpha_c = _c(br_alpha)
         C0 = nb * P
@@ -858,9 +880,10 @@ class PyrBodyBNFn(torch.autograd.Function):
                                                 _p(st2[0]), _p(st2[1]), _p(st2[2]), _p(st2[3]), _p(nbt2), _stream()))
         y = ops.pointwise(mraw, Epi(st2[2], st2[3], m_alpha), out=y)
         ctx.save_for_backward(x, zcat, mraw, st0, st2, br_alpha_c, merge_w, m_alpha, g0, g2, ws2, *stage_ws, *[pooled[i] for i in down])
-        ctx.sizes, ctx.down = [tuple(int(v) for v in s_) for s_ in sizes], down
-        ctx.sinks = ([_sink(t) for t in (br_gamma, br_beta, br_alpha, merge_w, m_gamma, m_beta, m_alpha)],
-                     [_sink(t) for t in stage_ws])
+        ctx.sizes, ctx.down = sizes, down
+        ctx.g_bn0, ctx.g_br_alpha = GradDstPair(br_gamma, br_beta), GradDst(br_alpha)                   # merge_layer.0
+        ctx.g_merge_w, ctx.g_bn2, ctx.g_m_alpha = GradDst(merge_w), GradDstPair(m_gamma, m_beta), GradDst(m_alpha)   # merge_layer.2
+        ctx.g_stage = [GradDst(t) for t in stage_ws]
         return y
 
     @staticmethod
@@ -869,24 +892,16 @@ class PyrBodyBNFn(torch.autograd.Function):
         x, zcat, mraw, st0, st2, br_alpha, merge_w, m_alpha, g0, g2, ws2 = sv[:11]
         sizes, down = ctx.sizes, ctx.down
         nb = len(sizes)
-        stage_ws = sv[11:11 + nb]
-        pooled = dict(zip(down, sv[11 + nb:]))
         gy = _c(gy)
         N, P, h, w = x.shape
         dev = x.device
         C0 = nb * P
-        psinks, wsinks = ctx.sinks
-
-        def dst(sink, shape):
-            return sink if sink is not None else torch.zeros(shape, device=dev, dtype=torch.float32)
         # merge_layer.2's BatchNorm + PReLU (batch statistics): direct path + statistics path
-        direct2 = psinks[4] is not None and psinks[5] is not None
         out2 = torch.empty(4, P, dtype=torch.float32, device=dev)             # d gamma, d beta, p, q
-        gal2 = dst(psinks[6], (P,)) if m_alpha is not None else None
+        direct2, d_gamma2, d_beta2 = ctx.g_bn2.bufs(out2[0], out2[1])
         check(lib.mspl_bn_train_prelu_bwd(_p(mraw), None, _p(gy), _p(st2[2]), _p(st2[3]), _p(m_alpha), _p(g2), _p(st2[0]), _p(st2[1]),
-                                          N, P, h * w, None, None, _p(ws2), 1 if direct2 else 0,
-                                          _p(psinks[4] if direct2 else out2[0]), _p(psinks[5] if direct2 else out2[1]), _p(gal2),
-                                          _p(out2[2]), _p(out2[3]), _stream()))
+                                          N, P, h * w, None, None, _p(ws2), direct2, _p(d_gamma2), _p(d_beta2),
+                                          _p(ctx.g_m_alpha.buf(zeroed=True)), _p(out2[2]), _p(out2[3]), _stream()))
         g_mraw = torch.empty_like(mraw)                                       # p * z + q + gc, gc recomputed from (z, gy)
         check(lib.mspl_bn_train_prelu_bwd_apply(_p(mraw), _p(gy), _p(st2[2]), _p(st2[3]), _p(m_alpha), _p(out2[2]), _p(out2[3]), N, P,
                                                 h * w, _p(g_mraw), _stream()))
@@ -894,45 +909,26 @@ class PyrBodyBNFn(torch.autograd.Function):
         zbuf = torch.zeros(2 * C0 + 2 * P, device=dev, dtype=torch.float32)   # one fill for both accumulators
         raw0 = zbuf[:2 * C0].view(2, C0)
         scratch2 = zbuf[2 * C0:].view(2, P)                                   # (merge_layer.2 is the identity here: sums not used)
-        g_br_alpha = dst(psinks[2], (C0,))
-        g_merge_w = dst(psinks[3], tuple(merge_w.shape))
+        g_br_alpha, g_merge_w = ctx.g_br_alpha.buf(zeroed=True), ctx.g_merge_w.buf(zeroed=True)
         gt = torch.empty((nb, N, P, h, w), device=dev, dtype=torch.float32)
         check(lib.mspl_pyrpool_merge_bwd(_p(g_mraw), _p(mraw), _p(zcat), N, P, h, w, nb, _p(st0[2]), _p(st0[3]), _p(br_alpha), None, None,
                                          _p(merge_w), _p(_const_vec(1.0, P, dev)), _p(_const_vec(0.0, P, dev)), None, None, None, _p(gt),
                                          _p(raw0[0]), _p(raw0[1]), _p(g_br_alpha), _p(g_merge_w), _p(scratch2[0]), _p(scratch2[1]), None,
                                          _stream()))
-        direct0 = psinks[0] is not None and psinks[1] is not None
         out0 = torch.empty(4, C0, dtype=torch.float32, device=dev)            # d gamma, d beta, p, q
+        direct0, d_gamma0, d_beta0 = ctx.g_bn0.bufs(out0[0], out0[1])
         check(lib.mspl_bn_batch_stats_bwd_coeffs(_p(raw0[0]), _p(raw0[1]), _p(g0), _p(st0[0]), _p(st0[1]), _p(st0[2]), C0,
-                                                 float(N * h * w), 1 if direct0 else 0, _p(psinks[0] if direct0 else out0[0]),
-                                                 _p(psinks[1] if direct0 else out0[1]), _p(out0[2]), _p(out0[3]), _stream()))
+                                                 float(N * h * w), direct0, _p(d_gamma0), _p(d_beta0), _p(out0[2]), _p(out0[3]),
+                                                 _stream()))
         check(lib.mspl_bn_stats_path_add(_p(gt), _p(zcat), _p(out0[2]), _p(out0[3]), N, P, nb, h * w, _stream()))
-        # the branches (as in PyrBodyFn)
-        g_stage = [dst(wsinks[i], tuple(stage_ws[i].shape)) for i in range(nb)]
-        adds = _pyr_down_backward(gt, (N, P, h, w), sizes, stage_ws, pooled, down, g_stage)
-        up = [i for i in range(nb) if i not in down]
-        nbp = len(up)
-        hsa = (ctypes.c_int32 * nbp)(*[sizes[i][0] for i in up])
-        wsa = (ctypes.c_int32 * nbp)(*[sizes[i][1] for i in up])
-        swp = (ctypes.c_void_p * nbp)(*[stage_ws[i].data_ptr() for i in up])
-        gtp = (ctypes.c_void_p * nbp)(*[gt[i].data_ptr() for i in up])
-        gwp = (ctypes.c_void_p * nbp)(*[g_stage[i].data_ptr() for i in up])
-        gx = torch.empty_like(x)
-        check(lib.mspl_pyrpool_branch_bwd(_p(x), N, P, h, w, nbp, hsa, wsa, swp, gtp, gwp, _p(adds[0] if adds else None),
-                                          _p(adds[1] if len(adds) > 1 else None), _p(gx), _stream()))
-        ret = lambda sink, t: None if sink is not None else t          # noqa: E731
-        return (gx, None, None, None,
-                None if direct0 else out0[0], None if direct0 else out0[1], ret(psinks[2], g_br_alpha), ret(psinks[3], g_merge_w),
-                None if direct2 else out2[0], None if direct2 else out2[1],
-                None if m_alpha is None else ret(psinks[6], gal2),
-                *[ret(wsinks[i], g_stage[i]) for i in range(nb)])
+        gx, g_stage_ws = _pyr_branch_backward(x, gt, sizes, down, sv[11:], ctx.g_stage)
+        return (gx, None, None, None, *ctx.g_bn0.results(), ctx.g_br_alpha.result(), ctx.g_merge_w.result(), *ctx.g_bn2.results(),
+                ctx.g_m_alpha.result(), *g_stage_ws)
 
 
 def bn_train_params(bn, device):
     """(running_mean, running_var, eps, momentum, workspace, num_batches_tracked) of a BatchNorm2d in train() for the fused nodes."""
-    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-        raise RuntimeError('mspl_amd: BatchNorm2d variants without momentum / running statistics / affine parameters are '
-                           'not on the path (the reference uses the defaults everywhere)')
+    _require_default_bn(bn)
     return (bn.running_mean, bn.running_var, float(bn.eps), float(bn.momentum), _bn_workspace(bn, device), _bn_nbt(bn))
 
 
@@ -1034,9 +1030,6 @@ class AdaptivePoolFn(torch.autograd.Function):
         return gx, None
 
 
-_GATE_EXPANDED = os.environ.get('MSPL_GATE_EXPANDED', '1') != '0'      # A/B aid
-
-
 class GapGateFn(torch.autograd.Function):
     """gate = sigmoid(W . mean_hw(x)) -> (N, Cout)."""
 
@@ -1050,7 +1043,7 @@ class GapGateFn(torch.autograd.Function):
         check(lib.mspl_gap_gate_fwd(_p(x), _p(w), N, Cin, Cout, H * W, _p(mean), _p(gate), _stream()))
         ctx.save_for_backward(mean, gate, w)
         ctx.shape = x.shape
-        ctx.wsink = _sink(w)
+        ctx.g_w = GradDst(w)
         return gate
 
     @staticmethod
@@ -1059,12 +1052,9 @@ class GapGateFn(torch.autograd.Function):
         N, Cin, H, W = ctx.shape
         Cout = w.shape[0]
         gmean = torch.empty_like(mean)
-        if ctx.wsink is not None:      # atomically into the parameter's gradient buffer (other micro-batch lanes add to it as well)
-            gw = None
-            check(lib.mspl_gap_gate_bwd_accum(_p(_c(ggate)), _p(gate), _p(mean), _p(w), N, Cin, Cout, _p(ctx.wsink), _p(gmean), _stream()))
-        else:
-            gw = torch.empty_like(w)
-            check(lib.mspl_gap_gate_bwd(_p(_c(ggate)), _p(gate), _p(mean), _p(w), N, Cin, Cout, _p(gw), _p(gmean), _stream()))
+        # a sink: atomically into the parameter's gradient buffer (other micro-batch lanes add to it as well)
+        bwd = lib.mspl_gap_gate_bwd_accum if ctx.g_w.is_sink else lib.mspl_gap_gate_bwd
+        check(bwd(_p(_c(ggate)), _p(gate), _p(mean), _p(w), N, Cin, Cout, _p(ctx.g_w.buf(zeroed=False)), _p(gmean), _stream()))
         gx = None
         if ctx.needs_input_grad[0]:
             if _GATE_EXPANDED:
@@ -1076,7 +1066,7 @@ class GapGateFn(torch.autograd.Function):
             else:
                 gx = torch.empty(ctx.shape, device=w.device, dtype=torch.float32)
                 check(lib.mspl_plane_broadcast(_p(gmean), N * Cin, H * W, 1.0 / (H * W), 0, _p(gx), _stream()))
-        return gx, gw
+        return gx, ctx.g_w.result()
 
 
 class FusionGateFn(torch.autograd.Function):
@@ -1212,7 +1202,7 @@ class DownTailFn(torch.autograd.Function):
         y = torch.empty((N, C) + tuple(a.shape[2:]), device=a.device, dtype=torch.float32)
         check(lib.mspl_down_tail_fwd(_p(a), _p(b), _p(reinf), _p(alpha), N, nin, C, hw, _p(y), _stream()))
         ctx.save_for_backward(a, b, alpha, reinf)
-        ctx.sink = _sink(alpha)
+        ctx.g_alpha = GradDst(alpha)
         return y
 
     @staticmethod
@@ -1224,9 +1214,9 @@ class DownTailFn(torch.autograd.Function):
         hw = a[0, 0].numel()
         ga, gb = torch.empty_like(a), torch.empty_like(b)
         gr = torch.empty_like(reinf) if reinf is not None else None
-        gal = ctx.sink if ctx.sink is not None else torch.zeros(C, device=a.device)
-        check(lib.mspl_down_tail_bwd(_p(a), _p(b), _p(reinf), _p(gy), _p(alpha), N, nin, C, hw, _p(ga), _p(gb), _p(gr), _p(gal), _stream()))
-        return ga, gb, (None if ctx.sink is not None else gal), gr
+        check(lib.mspl_down_tail_bwd(_p(a), _p(b), _p(reinf), _p(gy), _p(alpha), N, nin, C, hw, _p(ga), _p(gb), _p(gr),
+                                     _p(ctx.g_alpha.buf(zeroed=True)), _stream()))
+        return ga, gb, ctx.g_alpha.result(), gr
 
 
 def down_tail(a, b, alpha, reinf=None):
@@ -1250,6 +1240,12 @@ def frozen_bn_inv(bn):
             c = (key, torch.rsqrt(rv + bn.eps))
         bn.__dict__['_mspl_inv'] = c
     return c[1]
+
+
+def frozen_bn_fold(bn, scale, shift):
+    """A frozen BatchNorm as the fused nodes (EESPFn, PyrBodyFn) take it: its current no-grad fold (scale, shift) and what the
+    backward needs to turn d scale / d shift into d gamma / d beta."""
+    return {'scale': scale, 'shift': shift, 'mean': bn.running_mean, 'inv': frozen_bn_inv(bn)}
 
 
 def conv_bn_prelu(x, w, stride, groups, bn, scale, shift, alpha=None, pre_add=None, residual=None):
@@ -1301,12 +1297,31 @@ class BNBatchStatsFn(torch.autograd.Function):
         return gz, out[0], gsh, None, None, None, None
 
 
+def _bn_train_forward(z, residual, gamma, beta, alpha, running_mean, running_var, eps, momentum, ws, nbt):
+    """y = PReLU(BatchNorm_train(z) + residual) -> (y, st = (mean, invstd, scale, shift) rows, small).  small planes: the channel's
+    whole node in one workgroup, one launch (statistics + fold + apply); else the statistics + fold launch and the affine / PReLU one."""
+    N, C = z.shape[:2]
+    hw = z[0, 0].numel()
+    st = torch.empty(4, C, dtype=torch.float32, device=z.device)
+    small = _SMALL_BN and bool(lib.mspl_bn_train_small_fits(N, C, hw))
+    if small:
+        y = torch.empty_like(z)
+        check(lib.mspl_bn_train_small_fwd(_p(z), _p(residual), _p(gamma), _p(beta), _p(None if alpha is None else _c(alpha)), N, C, hw,
+                                          eps, momentum, _p(running_mean), _p(running_var), _p(nbt), _p(st[0]), _p(st[1]), _p(st[2]),
+                                          _p(st[3]), _p(y), _stream()))
+    else:
+        check(lib.mspl_bn_batch_stats_fused_fwd(_p(z), N, C, hw, eps, momentum, _p(running_mean), _p(running_var), _p(gamma),
+                                                _p(beta), _p(ws), _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]), _p(nbt), _stream()))
+        y = ops.pointwise(z, Epi(st[2], st[3], alpha, residual=residual))
+    return y, st, small
+
+
 class BNTrainPReLUFn(torch.autograd.Function):
     """y = PReLU(BatchNorm_train(z) + residual) with batch statistics (nn.BatchNorm2d in train(), the supervised loop), as ONE
     autograd node of FOUR launches: statistics + fold (the workgroup that adds a channel's last partial finishes the channel), the
     affine / PReLU kernel; backward: the affine backward whose last workgroup per channel turns the sums into (d gamma, d beta, p, q),
-    and ONE launch gz = p * z + q + gc (without a residual gc is recomputed there from (z, gy), not stored and read back).  `ws`: the BatchNorm's persistent workspace (zeroed once, handed back zeroed by both
-    kernels: no memset, no finalize launch, no coefficient launch, no zeros() per call -- eight launches before).  As two nodes
+    and ONE launch gz = p * z + q + gc (without a residual gc is recomputed there from (z, gy), not stored and read back).
+    `ws`: the BatchNorm's persistent workspace (zeroed once, handed back zeroed by both kernels: no memset, no finalize launch, no coefficient launch, no zeros() per call -- eight launches before).  As two nodes
     (BNBatchStatsFn + AffinePReLUFn) autograd added the two full-size gradients of z with an ATen kernel per BatchNorm and accumulated
     d gamma / d beta with two more (320 `add_` launches, 1.85 ms of a 17.5 ms iteration)."""
 
@@ -1314,23 +1329,10 @@ class BNTrainPReLUFn(torch.autograd.Function):
     def forward(ctx, z, gamma, beta, alpha, residual, running_mean, running_var, eps, momentum, ws, nbt):
         z = _c(z)
         residual = None if residual is None else _c(residual)
-        N, C = z.shape[:2]
-        hw = z[0, 0].numel()
-        st = torch.empty(4, C, dtype=torch.float32, device=z.device)       # mean, invstd, scale, shift
-        gamma_c, beta_c = _c(gamma), _c(beta)
-        ctx.small = _SMALL_BN and bool(lib.mspl_bn_train_small_fits(N, C, hw))
-        if ctx.small:
-            # small planes: the channel's whole node in one workgroup, one launch (statistics + fold + apply)
-            y = torch.empty_like(z)
-            check(lib.mspl_bn_train_small_fwd(_p(z), _p(residual), _p(gamma_c), _p(beta_c), _p(None if alpha is None else _c(alpha)), N, C, hw,
-                                              eps, momentum, _p(running_mean), _p(running_var), _p(nbt), _p(st[0]), _p(st[1]), _p(st[2]),
-                                              _p(st[3]), _p(y), _stream()))
-        else:
-            check(lib.mspl_bn_batch_stats_fused_fwd(_p(z), N, C, hw, eps, momentum, _p(running_mean), _p(running_var), _p(gamma_c),
-                                                    _p(beta_c), _p(ws), _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]), _p(nbt), _stream()))
-            y = ops.pointwise(z, Epi(st[2], st[3], alpha, residual=residual))
+        gamma_c = _c(gamma)
+        y, st, ctx.small = _bn_train_forward(z, residual, gamma_c, _c(beta), alpha, running_mean, running_var, eps, momentum, ws, nbt)
         ctx.save_for_backward(z, gamma_c, alpha, residual, st, ws)
-        ctx.sinks = (_sink(gamma), _sink(beta), _sink(alpha))
+        ctx.g_bn, ctx.g_alpha = GradDstPair(gamma, beta), GradDst(alpha)
         return y
 
     @staticmethod
@@ -1340,40 +1342,32 @@ class BNTrainPReLUFn(torch.autograd.Function):
         gy = _c(gy)
         N, C = z.shape[:2]
         hw = z[0, 0].numel()
-        s_g, s_b, s_a = ctx.sinks
         gres = torch.empty_like(z) if residual is not None else None
+        gal = ctx.g_alpha.buf(zeroed=True)
+        out = torch.empty(2 if ctx.small else 4, C, dtype=torch.float32, device=z.device)      # d gamma, d beta[, p, q]
+        direct, d_gamma, d_beta = ctx.g_bn.bufs(out[0], out[1])
         if ctx.small:
-            gal = None
-            if alpha is not None:
-                gal = s_a if s_a is not None else torch.zeros(C, device=z.device)
-            direct = s_g is not None and s_b is not None
-            out = torch.empty(2, C, dtype=torch.float32, device=z.device)
             gz = torch.empty_like(z)
             check(lib.mspl_bn_train_small_bwd(_p(z), _p(residual), _p(gy), _p(scale), _p(shift), _p(alpha), _p(gamma), _p(mean), _p(invstd),
-                                              N, C, hw, 1 if direct else 0, _p(gz), _p(gres), _p(s_g if direct else out[0]),
-                                              _p(s_b if direct else out[1]), _p(gal), _stream()))
-            return (gz, None if direct else out[0], None if direct else out[1],
-                    None if (alpha is None or s_a is not None) else gal, gres, None, None, None, None, None, None)
-        gc = torch.empty_like(z) if residual is not None else None       # no residual: the second pass recomputes it from (z, gy)
-        gal = None
-        if alpha is not None:
-            gal = s_a if s_a is not None else torch.zeros(C, device=z.device)
-        direct = s_g is not None and s_b is not None
-        out = torch.empty(4, C, dtype=torch.float32, device=z.device)      # d gamma, d beta, p, q
-        check(lib.mspl_bn_train_prelu_bwd(_p(z), _p(residual), _p(gy), _p(scale), _p(shift), _p(alpha), _p(gamma), _p(mean), _p(invstd),
-                                          N, C, hw, _p(gres), _p(gc), _p(ws), 1 if direct else 0, _p(s_g if direct else out[0]),
-                                          _p(s_b if direct else out[1]), _p(gal), _p(out[2]), _p(out[3]), _stream()))
-        if gc is not None:
-            gz = ops.pointwise(z, Epi(out[2], out[3], residual=gc))       # p * z + q + gc
+                                              N, C, hw, direct, _p(gz), _p(gres), _p(d_gamma), _p(d_beta), _p(gal), _stream()))
         else:
-            gz = torch.empty_like(z)
-            check(lib.mspl_bn_train_prelu_bwd_apply(_p(z), _p(gy), _p(scale), _p(shift), _p(alpha), _p(out[2]), _p(out[3]), N, C, hw,
-                                                    _p(gz), _stream()))
-        return (gz, None if direct else out[0], None if direct else out[1],
-                None if (alpha is None or s_a is not None) else gal, gres, None, None, None, None, None, None)
+            gc = torch.empty_like(z) if residual is not None else None       # no residual: the second pass recomputes it from (z, gy)
+            check(lib.mspl_bn_train_prelu_bwd(_p(z), _p(residual), _p(gy), _p(scale), _p(shift), _p(alpha), _p(gamma), _p(mean), _p(invstd),
+                                              N, C, hw, _p(gres), _p(gc), _p(ws), direct, _p(d_gamma), _p(d_beta), _p(gal), _p(out[2]),
+                                              _p(out[3]), _stream()))
+            if gc is not None:
+                gz = ops.pointwise(z, Epi(out[2], out[3], residual=gc))       # p * z + q + gc
+            else:
+                gz = torch.empty_like(z)
+                check(lib.mspl_bn_train_prelu_bwd_apply(_p(z), _p(gy), _p(scale), _p(shift), _p(alpha), _p(out[2]), _p(out[3]), N, C, hw,
+                                                        _p(gz), _stream()))
+        return (gz, *ctx.g_bn.results(), ctx.g_alpha.result(), gres, None, None, None, None, None, None)
 
 
-_SMALL_BN = os.environ.get('MSPL_BN_SMALL', '1') != '0'       # small planes: one launch per BatchNorm node and direction
+def _require_default_bn(bn):
+    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+        raise RuntimeError('mspl_amd: BatchNorm2d variants without momentum / running statistics / affine parameters are '
+                           'not on the path (the reference uses the defaults everywhere)')
 
 
 def _bn_nbt(bn):
@@ -1399,9 +1393,7 @@ def _bn_workspace(bn, device):
 
 def bn_train_prelu(z, bn, alpha=None, residual=None):
     """PReLU(bn(z) + residual) for a BatchNorm2d in train(); updates its running statistics like nn.BatchNorm2d does."""
-    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-        raise RuntimeError('mspl_amd: BatchNorm2d variants without momentum / running statistics / affine parameters are '
-                           'not on the path (the reference uses the defaults everywhere)')
+    _require_default_bn(bn)
     nbt = _bn_nbt(bn)                     # incremented by the statistics kernel (an int64 CUDA scalar; nn.BatchNorm2d adds 1 per forward)
     return BNTrainPReLUFn.apply(z, bn.weight, bn.bias, alpha, residual, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
                                 _bn_workspace(bn, z.device), nbt)
@@ -1410,9 +1402,7 @@ def bn_train_prelu(z, bn, alpha=None, residual=None):
 def bn_batch_stats(z, bn):
     """(scale, shift) of a BatchNorm2d in train() for the batch z; updates running_mean / running_var /
     num_batches_tracked like nn.BatchNorm2d does."""
-    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-        raise RuntimeError('mspl_amd: BatchNorm2d variants without momentum / running statistics / affine parameters are '
-                           'not on the path (the reference uses the defaults everywhere)')
+    _require_default_bn(bn)
     out = BNBatchStatsFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
     with torch.no_grad():
         bn.num_batches_tracked += 1

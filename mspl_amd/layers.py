@@ -429,14 +429,12 @@ class EESP(nn.Module):
         pj, br, exp = self.proj_1x1, self.br_after_cat, self.conv_1x1_exp
         if _FUSED_EESP_TRAIN and not (pj.bn.training or br.bn.training or exp.bn.training):
             # the whole block as one autograd node (frozen BatchNorms): autograd.EESPFn
-            def fold(bn):
-                scale, shift = train_fold(bn)
-                return {'scale': scale, 'shift': shift, 'mean': bn.running_mean, 'inv': ag.frozen_bn_inv(bn)}
             strided_avg = self.stride == 2 and self.downAvg
             residual = (not strided_avg) and self.stride == 1 and exp.conv.out_channels == input.shape[1]
             cfg = {'stride': self.stride, 'dil': tuple(self.dilations), 'groups': pj.conv.groups, 'residual': residual}
             ws = [m.conv.weight for m in self.spp_dw]
-            return ag.EESPFn.apply(input, cfg, fold(pj.bn), fold(br.bn), fold(exp.bn), pj.conv.weight, pj.bn.weight, pj.bn.bias,
+            folds = [ag.frozen_bn_fold(bn, *train_fold(bn)) for bn in (pj.bn, br.bn, exp.bn)]
+            return ag.EESPFn.apply(input, cfg, *folds, pj.conv.weight, pj.bn.weight, pj.bn.bias,
                                    pj.act.weight, ws[0], ws[1], ws[2], ws[3], br.bn.weight, br.bn.bias, br.act.weight,
                                    exp.conv.weight, exp.bn.weight, exp.bn.bias, None if strided_avg else self.module_act.weight)
         has_res = self.stride == 1 and exp.conv.out_channels == input.shape[1] and not (self.stride == 2 and self.downAvg)
@@ -734,11 +732,8 @@ class EfficientPyrPool(nn.Module):
         bn0, act0 = self.merge_layer[0].br[0], self.merge_layer[0].br[1]
         mcbr = self.merge_layer[2].cbr
         conv2, bn2, act2 = mcbr[0], mcbr[1], mcbr[2]
-
-        def fold(bn):
-            scale, shift = train_fold(bn)
-            return {'scale': scale, 'shift': shift, 'mean': bn.running_mean, 'inv': ag.frozen_bn_inv(bn)}
-        return ag.PyrBodyFn.apply(x, sizes, fold(bn0), fold(bn2), bn0.weight, bn0.bias, act0.weight, conv2.weight, bn2.weight,
+        folds = [ag.frozen_bn_fold(bn, *train_fold(bn)) for bn in (bn0, bn2)]
+        return ag.PyrBodyFn.apply(x, sizes, *folds, bn0.weight, bn0.bias, act0.weight, conv2.weight, bn2.weight,
                                   bn2.bias, act2.weight, *[st.weight for st in self.stages])
 
     def _body_train_bn(self, x, sizes):
