@@ -91,6 +91,9 @@ class EESPNet(nn.Module):
         _init_params(self)
 
 
+_GATE_CAT_MAX_K = 512         # training path: widest concatenation the gate's 1x1 takes in one launch (the kernel stages K weights per row in LDS)
+
+
 class FusionGate(nn.Module):
     """RGB-D fusion gate (nn_layers/fusion_gate.py:11-47): out = rgb*w + depth*(1-w), w = sigmoid(conv_1x1(cat(rgb, depth))),
     or rgb + depth when not trainable.  The concatenation is never materialised on the inference path: the 1x1 runs as two
@@ -110,7 +113,15 @@ class FusionGate(nn.Module):
                                % (self.nchannel, tuple(rgb.shape), tuple(depth.shape)))
         w = self.conv_1x1.conv.weight
         if _training_path():
-            z = ag.conv(torch.cat((rgb, depth), 1), w) if self.is_trainable else None
+            c = self.nchannel
+            if not self.is_trainable:
+                z = None
+            elif 2 * c > _GATE_CAT_MAX_K:
+                # level 4 of the s=2.0 net (K = 1024): beyond the weight tile of the 1x1 kernel, which refuses it.  The two halves of
+                # the weight instead, as on the inference path; autograd adds the halves' gradients back into the weight's
+                z = ag.conv(rgb, w[:, :c]) + ag.conv(depth, w[:, c:])
+            else:
+                z = ag.conv(torch.cat((rgb, depth), 1), w)
             return ag.FusionGateFn.apply(z, rgb, depth)
         if not self.is_trainable:
             return ops.fusion_gate(None, rgb, depth)

@@ -36,7 +36,8 @@ def train_step(sd, param_names, x, labels, class_weights, ignore_idx, lr=5e-4, w
     return loss.detach(), gmap, new
 
 
-def supervised_step(sd, groups, x, labels, class_weights, ignore_idx, momentum=0.9, weight_decay=4e-5, b=0.015, x_d=None):
+def supervised_step(sd, groups, x, labels, class_weights, ignore_idx, momentum=0.9, weight_decay=4e-5, b=0.015, x_d=None,
+                    dense_fuse=False, trainable_fusion=True):
     """One iteration of train_seg_ue (utilities/train_eval_seg.py:179-225) with torch.optim.SGD over learning-rate groups
     (train_segmentation.py:244-253): model.train() -> batch-statistics BatchNorm, loss = CrossEntropy(main + 0.5*aux)
     (ignore_index, class weights), flooding (loss-b).abs()+b, first SGD step (momentum buffer = g + wd*p).
@@ -50,9 +51,9 @@ def supervised_step(sd, groups, x, labels, class_weights, ignore_idx, momentum=0
             params[n] = sd[n].clone().requires_grad_(True)
             work[n] = params[n]
     with onet.bn_training():
-        main, aux = onet.espdnet_ue_forward(work, x, x_d)
+        main, aux = onet.espdnet_ue_forward(work, x, x_d, dense_fuse=dense_fuse, trainable_fusion=trainable_fusion)
     out = main + 0.5 * aux
-    w = None if class_weights is None else class_weights.float()
+    w = None if class_weights is None else class_weights.to(out.dtype)       # float32 by default; the float64 oracle of the tests
     loss = torch.nn.functional.cross_entropy(out, labels, weight=w, ignore_index=ignore_idx).mean()
     loss = (loss - b).abs() + b
     grads = torch.autograd.grad(loss, list(params.values()), allow_unused=True)

@@ -58,6 +58,52 @@ def assert_grads_match(got, ref, tau_rel, tau_el, n_expected=None, floor_rel=1e-
     return worst_rel, worst_el
 
 
+SEG_PREFIXES = ('bu_dec_l1.', 'bu_dec_l2.', 'bu_dec_l3.', 'bu_dec_l4.', 'merge_enc_dec_l4.', 'merge_enc_dec_l3.', 'merge_enc_dec_l2.',
+                'bu_br_l4.', 'bu_br_l3.', 'bu_br_l2.')
+
+
+def supervised_groups(names, lr=0.009, lr_mult=10.0, use_depth=False):
+    """The SGD groups of the supervised loop as oracle.train.supervised_step takes them: base net at lr, segmentation head (and, with
+    a depth image, the depth encoder) at lr * lr_mult.  Every other parameter (auxiliary decoder, fusion gates, the depth encoder's
+    blocks the RGB path borrows) is in no group of the loop: it goes into a last group with lr 0, so the oracle returns its gradient
+    and leaves its value alone."""
+    base = [n for n in names if n.startswith('base_net.')]
+    seg = [n for n in names if n.startswith(SEG_PREFIXES)]
+    dep = [n for n in names if n.startswith('depth_base_net.')] if use_depth else []
+    taken = set(base) | set(seg) | set(dep)
+    groups = [(base, lr), (seg, lr * lr_mult)] + ([(dep, lr * lr_mult)] if use_depth else [])
+    return groups + [([n for n in names if n not in taken], 0.0)]
+
+
+class BatchNormRecorder:
+    """Records, for every F.batch_norm call while the oracle runs, the number of values per channel behind its running_var buffer
+    and how often the buffer was used (keyed by the buffer's storage): what a test needs to restate the unbiased-variance factor
+    n / (n - 1) for another batch size, and to know num_batches_tracked after the step (with a depth image the RGB and the depth
+    branch share some blocks, whose BatchNorms then run twice per forward)."""
+
+    def __init__(self, monkeypatch):
+        self.count = {}
+        batch_norm = F.batch_norm
+
+        def rec(x, running_mean, running_var, *a, **k):
+            calls = self.count.get(running_var.data_ptr(), (0, 0))[1]
+            self.count[running_var.data_ptr()] = (x.numel() // x.shape[1], calls + 1)
+            return batch_norm(x, running_mean, running_var, *a, **k)
+        monkeypatch.setattr(torch.nn.functional, 'batch_norm', rec)
+
+    def per_channel(self, after):
+        """{running_var key: (values per channel, calls)} for the oracle's returned state dict."""
+        return {k: self.count[v.data_ptr()] for k, v in after.items() if k.endswith('running_var') and v.data_ptr() in self.count}
+
+
+def running_var_for_copies(before, after, n, copies, momentum=0.1):
+    """running_var after one step on `copies` permuted copies of the batch, from the oracle's value for the batch alone (n values per
+    channel): the biased batch variance is the same, the unbiased factor becomes copies * n / (copies * n - 1).  float64."""
+    var_b = (after - (1 - momentum) * before) / (momentum * n / (n - 1.0))
+    m = float(copies * n)
+    return (1 - momentum) * before + momentum * var_b * (m / (m - 1.0))
+
+
 class ActivationRecorder:
     """Records every input of F.prelu / F.relu while the oracle runs (installed with pytest's monkeypatch): the cases' conditioning.
     A PReLU input within float32 rounding of zero can take the other slope on the GPU, and on maps of a few pixels that moves a

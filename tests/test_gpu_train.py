@@ -605,11 +605,13 @@ def test_fused_pyramid_training_equals_node_per_op(cfg):
 
 
 @pytest.mark.parametrize('cfg', [(2, 32, 24, 16, 30, True), (2, 24, 5, 32, 60, False), (1, 16, 13, 64, 120, False),
-                                 (2, 16, 20, 18, 34, True), (4, 48, 32, 40, 72, True), (3, 16, 8, 8, 12, True)])
+                                 (2, 16, 20, 18, 34, True), (4, 48, 32, 40, 72, True), (3, 16, 8, 8, 12, True),
+                                 (16, 32, 24, 72, 120, True)])      # the last: a large plane (N * h * w above the one-launch BatchNorm rule)
 def test_fused_pyramid_batch_statistics_equals_node_per_op(cfg):
     """autograd.PyrBodyBNFn (BatchNorms in train(): the supervised loop) against the node-per-op training path: output, input gradient,
     every parameter gradient, and the BatchNorms' buffers (running statistics, num_batches_tracked) after the step."""
     from mspl_amd import autograd as ag, layers
+    from mspl_amd._native import lib
     N, cin, cout, h, w, last_br = cfg
     m = _pyr_module(cin, cout, last_br, 79).train()
     assert ag.pyr_body_fits((N, 16, h, w), m.branch_sizes(h, w)) and (h * w) % 4 == 0
@@ -637,11 +639,25 @@ def test_fused_pyramid_batch_statistics_equals_node_per_op(cfg):
             ag.PyrBodyBNFn.apply = orig
     assert calls == [True]
     close(res[True][0], res[False][0], atol=5e-5, rtol=2e-4)
-    close(res[True][1], res[False][1], atol=1e-4, rtol=2e-3)
+    # The large plane holds 18.8 M PReLU inputs, and two float32 evaluations of them do not agree on every sign: the float32 ORACLE of
+    # this block takes the other slope at 9 of them against float64.  One such input moves the gradient by (1 - alpha) * g in a
+    # neighbourhood that the pyramid's down-sampled branches widen to thousands of elements (float32 oracle: 1.2 % of the input
+    # gradient beyond the tolerance below, parameter gradients off by up to 3.3e-3 of their largest element).  So there the input
+    # gradient may miss the element tolerance on 5 % of its elements -- a wrong coefficient, term or channel misses it on all of
+    # them -- and each of the two paths gets the float32 oracle's 3.3e-3 for the parameter gradients.
+    large = not lib.mspl_bn_train_small_fits(N, 16, h * w)
+    assert large == (cfg[0] == 16)
+    if large:
+        a, b = res[True][1], res[False][1]
+        off = float(((a - b).abs() > 1e-4 + 2e-3 * b.abs()).float().mean())
+        print('large plane: %.4f of the input gradient beyond the element tolerance' % off)
+        assert off <= 0.05, off
+    else:
+        close(res[True][1], res[False][1], atol=1e-4, rtol=2e-3)
     for k in res[False][2]:
         a, b = res[True][2][k], res[False][2][k]
         scale = float(b.abs().max()) + 1e-6
-        assert float((a - b).abs().max()) <= 3e-3 * scale + 2e-5, (k, float((a - b).abs().max()), scale)
+        assert float((a - b).abs().max()) <= (6.6e-3 if large else 3e-3) * scale + 2e-5, (k, float((a - b).abs().max()), scale)
     for k, b in res[False][3].items():
         a = res[True][3][k]
         if b.dtype == torch.int64:
@@ -651,7 +667,10 @@ def test_fused_pyramid_batch_statistics_equals_node_per_op(cfg):
 
 
 @pytest.mark.parametrize('cfg', [(2, 64, 64, 7, 12, 20, 1), (1, 128, 128, 9, 9, 15, 1), (3, 256, 256, 9, 18, 30, 1), (16, 64, 64, 9, 36, 60, 1),
-                                 (2, 32, 96, 13, 16, 24, 2), (1, 64, 64, 9, 15, 21, 2), (1, 16, 16, 9, 40, 300, 1)])
+                                 (2, 32, 96, 13, 16, 24, 2), (1, 64, 64, 9, 15, 21, 2), (1, 16, 16, 9, 40, 300, 1),
+                                 # large planes (above the one-launch BatchNorm rule): mspl_eesp_bwd_fused_bnstat, and the strided block's
+                                 # mspl_hff_bn_stat_suffix_bwd
+                                 (16, 64, 64, 9, 72, 120, 1), (16, 32, 96, 13, 144, 240, 2)])
 def test_eesp_block_batch_statistics_fused_k2_node(cfg):
     """autograd.EespDwBNFn (K2 + br_after_cat in train(): BatchNorm sums launch + mspl_eesp_bwd_fused_bnstat) against the node-per-op
     form of the same block: output, input gradient, every parameter gradient, BatchNorm buffers."""

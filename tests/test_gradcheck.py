@@ -123,3 +123,77 @@ def test_activation_recorder_sees_near_kinks(monkeypatch):
     torch.nn.functional.prelu(small, torch.full((4,), 0.25))
     torch.nn.functional.relu(big)
     assert [(s, k) for _, s, k in rec.near_kinks()] == [((2, 4, 3, 5), 1)]
+
+
+# ------------------------------------------------------------------ the supervised step (batch-statistics BatchNorm)
+# The same proof for tests/test_gpu_supervised_grad_parity.py, with ITS constants: the float32 oracle's supervised gradients pass
+# against float64 at the small-case tolerances, and the slips a batch-statistics kernel can make fail.
+@pytest.fixture(scope='module')
+def supervised_grads():
+    """(float32 gradients, float64 gradients, run(dtype) for further float32 runs) of the smallest supervised case."""
+    from tests import test_gpu_supervised_grad_parity as sup
+    from tests.gradcheck import supervised_groups
+    case = sup.CASES[sup.SMALLEST]
+    m = case.model()
+    names = [n for n, _ in m.named_parameters()]
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    x, y, _ = case.data()
+
+    def run(dt):
+        sdt = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in sd.items()}
+        return otrain.supervised_step(sdt, supervised_groups(names, sup.LR, sup.LR_MULT), x.to(dt), y, None, case.ignore_idx,
+                                      sup.MOMENTUM, sup.WEIGHT_DECAY, sup.FLOOD)[1]
+    return run(torch.float32), run(torch.float64), run
+
+
+def _sup_check(got, ref):
+    from tests import test_gpu_supervised_grad_parity as sup
+    return assert_grads_match(got, ref, sup.SUP_TAU_REL, sup.SUP_TAU_EL, n_expected=340)
+
+
+def test_float32_oracle_supervised_passes(supervised_grads):
+    g32, g64, _ = supervised_grads
+    _sup_check(g32, g64)
+
+
+def test_supervised_statistics_as_constants_fail(supervised_grads, monkeypatch):
+    """A backward that treats the batch mean and variance as constants (the direct path alone, no p * z + q term)."""
+    from oracle import net as onet
+    _, g64, run = supervised_grads
+
+    def bn_detached(x, sd, p):
+        assert onet.BN_MODE['training']
+        mean = x.mean((0, 2, 3), keepdim=True).detach()
+        var = x.var((0, 2, 3), unbiased=False, keepdim=True).detach()
+        return (x - mean) / torch.sqrt(var + onet.BN_EPS) * sd[p + '.weight'].view(1, -1, 1, 1) + sd[p + '.bias'].view(1, -1, 1, 1)
+    monkeypatch.setattr(onet, '_bn', bn_detached)
+    with pytest.raises(AssertionError, match='gradients off'):
+        _sup_check(run(torch.float32), g64)
+
+
+def _bn_gamma_scaled(g, ref):
+    n = _smallest(ref, lambda n, r: n.endswith(('bn.weight', 'cbr.1.weight', 'br.0.weight')))
+    g[n] = g[n] * 1.01
+
+
+def _small_negated(g, ref):
+    n = _smallest(ref, lambda n, r: r.numel() <= 64)
+    g[n] = -g[n]
+
+
+@pytest.mark.parametrize('mutate', [_bn_gamma_scaled, _small_negated], ids=['bn_gamma_scaled_1.01', 'small_tensor_negated'])
+def test_each_supervised_mutation_fails(supervised_grads, mutate):
+    g32, g64, _ = supervised_grads
+    g = dict(g32)
+    mutate(g, g64)
+    with pytest.raises(AssertionError, match='gradients off'):
+        _sup_check(g, g64)
+
+
+def test_supervised_tensor_sets_must_agree(supervised_grads):
+    g32, g64, _ = supervised_grads
+    n = next(n for n, r in g64.items() if r is not None)
+    g = dict(g32)
+    g[n] = None
+    with pytest.raises(AssertionError, match='one side only'):
+        _sup_check(g, g64)

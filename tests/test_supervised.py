@@ -90,13 +90,22 @@ def test_bn_batch_stats_kernel():
         assert int(bn.num_batches_tracked) == 1
 
 
+BN_NODE_TWO_LAUNCH = {(16, 16, 72, 120), (4, 8, 144, 240), (8, 6, 75, 77)}      # the shapes that are there for the two-launch form
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('shp,mean_off,with_res', [((16, 24, 18, 30), 0.5, True), ((2, 7, 5, 9), 3.0, False), ((16, 8, 36, 60), -2.0, True),
-                                                   ((4, 32, 64, 120), 1.0, True), ((3, 5, 9, 15), 0.0, True), ((16, 16, 72, 120), 0.3, False)])
+@pytest.mark.parametrize('shp,mean_off,with_res', [
+    ((16, 24, 18, 30), 0.5, True), ((2, 7, 5, 9), 3.0, False), ((16, 8, 36, 60), -2.0, True),
+    ((4, 32, 64, 120), 1.0, True), ((3, 5, 9, 15), 0.0, True), ((16, 16, 72, 120), 0.3, False),
+    # the two-launch form WITH a residual (the gc + pointwise(p * z + q + gc) backward), and with planes that are not whole quads
+    ((16, 16, 72, 120), 0.3, True), ((4, 8, 144, 240), -1.0, True), ((8, 6, 75, 77), 0.7, True), ((8, 6, 75, 77), 0.7, False)])
 def test_bn_train_prelu_node(shp, mean_off, with_res):
     """autograd.bn_train_prelu (PReLU(BatchNorm_train(z) + residual), the supervised loop's node) against torch in fp64: the one-launch
-    small-plane form (N * HW <= 40 960: the first, second, third and fifth shapes) and the two-launch form, with and without residual."""
+    small-plane form (N * HW <= 40 960) and the two-launch form above it, with and without residual; the form a shape is there for is
+    checked against the library's own rule."""
     from mspl_amd import autograd as ag
+    from mspl_amd._native import lib
+    assert ag._SMALL_BN and bool(lib.mspl_bn_train_small_fits(shp[0], shp[1], shp[2] * shp[3])) == (shp not in BN_NODE_TWO_LAUNCH)
     g = torch.Generator().manual_seed(6)
     C = shp[1]
     z = (torch.randn(shp, generator=g) * 1.3 + mean_off).cuda().requires_grad_()
