@@ -231,6 +231,21 @@ int mspl_avgpool3x3s2_psum_fwd(const float* x, int32_t N, int32_t C, int32_t H, 
 int mspl_gate_from_sums_fwd(const float* psum, const float* w, int32_t N, int32_t Cin, int32_t Cout, int32_t nblk, int32_t HW,
                             float* gate, void* stream);
 
+/* Head of a DownSampler block in one launch (inference): the EESP branch's proj_1x1 (nn_layers/eesp.py:60-67: grouped 1x1 +
+ * BatchNorm + PReLU) and the pool branch with the block's epilogue (nn_layers/eesp.py:123-144) from ONE read of the input, + the
+ * plane sums of mspl_avgpool3x3s2_psum_fwd.  x (N,nin,H,W); wp (n, nin/groups), pscale / pshift / palpha (n): the projection;
+ * ep: the DownSampler epilogue on channels [0, nin) of `out` (scale, shift, alpha required, reinf_r / reinf_w optional, out_ctot =
+ * the block's output channels, out_coff = 0, nothing else).  Writes r (N,n,H,W) = what mspl_conv1x1_fwd gives (k ascending, the
+ * order of its vector-unit form), channels [0, nin) of out (N,out_ctot,H/2,W/2) and psum (N*nin, mspl_down_head_psum_blocks(H, W)),
+ * both bit-identical to mspl_avgpool3x3s2_psum_fwd's DownSampler form (one partial per workgroup of a plane, fixed-order adds, no
+ * atomics).  Covered (mspl_down_head_fits returns 1): groups = 4, n/4 in {6, 8}, nin/4 <= 64, H even, W % 8 == 0 -- levels 2 and 3
+ * of ESPDNet(-UE) s=2.0; callers run mspl_conv1x1_fwd + mspl_avgpool3x3s2_psum_fwd otherwise (_fwd returns MSPL_ERR_UNSUPPORTED). */
+int mspl_down_head_fits(int32_t N, int32_t nin, int32_t n, int32_t groups, int32_t H, int32_t W, uint32_t launch_flags);
+int mspl_down_head_psum_blocks(int32_t H, int32_t W);
+int mspl_down_head_fwd(const float* x, const float* wp, const float* pscale, const float* pshift, const float* palpha, int32_t N,
+                       int32_t nin, int32_t n, int32_t groups, int32_t H, int32_t W, const mspl_epilogue_t* ep, float* r, float* out,
+                       float* psum, void* stream);
+
 /* K6 prologue: the low-resolution branches' maps for mspl_pyrpool_fused_fwd in ONE launch (one workgroup per (image,
  *     channel) plane): out[i] (N,P,hs[i],ws[i]) = dw3x3(adaptive_avg_pool2d(x, (hs[i],ws[i]))) with stage_w[i] (P,1,3,3);
  *     nn_layers/efficient_pyramid_pool.py:44-50 for the scales < 1.  A workgroup stages a band of input rows and the

@@ -73,6 +73,9 @@ SIGNATURES = {
     'mspl_adaptive_avgpool_fwd': [c_f32p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _EP, c_f32p, ctypes.c_void_p],
     'mspl_avgpool3x3s2_psum_fwd': [c_f32p, c_i32, c_i32, c_i32, c_i32, _EP, c_f32p, c_f32p, ctypes.c_void_p],
     'mspl_avgpool3x3s2_psum_blocks': [c_i32, c_i32],
+    'mspl_down_head_fits': [c_i32] * 6 + [ctypes.c_uint32],
+    'mspl_down_head_psum_blocks': [c_i32, c_i32],
+    'mspl_down_head_fwd': [c_f32p] * 5 + [c_i32] * 6 + [_EP, c_f32p, c_f32p, c_f32p, ctypes.c_void_p],
     'mspl_gate_from_sums_fwd': [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32p, ctypes.c_void_p],
     'mspl_pointwise_fwd': [c_f32p, c_i32, c_i32, c_i32, _EP, c_f32p, ctypes.c_void_p],
     'mspl_gap_gate_fwd': [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, c_f32p, ctypes.c_void_p],

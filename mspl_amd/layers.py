@@ -199,6 +199,7 @@ _EESP_DW_BN = os.environ.get('MSPL_EESP_DW_BN', '1') != '0'    # EESP in train()
 _CONV_SKIP = os.environ.get('MSPL_CONV_SKIP', '1') != '0'      # EESP in train(): projection + skip connection as one autograd node
 _FUSED_BN_TRAIN = os.environ.get('MSPL_FUSED_BN_TRAIN', '1') != '0'      # batch-statistics BN + PReLU as one autograd node
 _FUSED_DW_EXP = os.environ.get('MSPL_EESP_EXP', '1') != '0'   # inference: K2 + K3 of a stride-1 EESP block as one launch
+_FUSED_DOWN_HEAD = os.environ.get('MSPL_DOWN_HEAD', '1') != '0'   # inference: a DownSampler's projection + pool + plane sums as one launch (ops.down_head)
 _FUSED_DEC_MERGE = True          # inference: skip 3x3 + up-merge + the next pyramid block's projection as one launch (ops.decoder_merge)
 _FUSED_NEXT_PROJ = os.environ.get('MSPL_EESP_NEXT', '1') != '0'   # ... and the following block's proj_1x1 inside that launch
 _FUSED_EESP_TRAIN = os.environ.get('MSPL_FUSED_EESP_TRAIN', '1') != '0'  # EESP block as one autograd node (frozen BatchNorm)
@@ -421,7 +422,11 @@ class EESP(nn.Module):
             ps, pb = bn_fold(pj.bn)
             return ops.eesp_proj_dw_hff(input, pj.conv.weight, ps, pb, pj.act.weight, self._dw_weights(), self.dilations,
                                         pj.conv.groups, Epi(scale, shift, self.br_after_cat.act.weight))
-        o1 = pj(input)
+        return self.transform(pj(input))
+
+    def transform(self, o1):
+        """K2 alone, for a reduced tensor some other launch has produced (DownSampler's head launch)."""
+        scale, shift = bn_fold(self.br_after_cat.bn)
         return ops.eesp_dw_hff(o1, self._dw_weights(), self.dilations, self.stride,
                                Epi(scale, shift, self.br_after_cat.act.weight))
 
@@ -602,6 +607,18 @@ class DownSampler(nn.Module):
             if r.shape[3] != Wo:
                 raise RuntimeError('The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton '
                                    'dimension 3' % (Wo, r.shape[3]))
+        pj = self.eesp.proj_1x1
+        if _FUSED_DOWN_HEAD and ops.down_head_fits(input.shape, pj.conv.out_channels, pj.conv.groups):
+            # projection + pool + plane sums from one read of `input` (csrc/down_head.hip); K2 and the expansion follow as before
+            join(0, (r,))
+            scale, shift, rw = self._epilogue_vectors(r is not None)
+            ep = Epi(scale, shift, self.act.weight, reinf_r=r, reinf_w=rw)
+            ps, pb = bn_fold(pj.bn)
+            o1, sums = ops.down_head(input, pj.conv.weight, ps, pb, pj.act.weight, pj.conv.groups, ep, out)
+            _remember_plane_sums(input, sums)
+            cat = self.eesp.transform(o1)
+            ops.conv1x1(cat, self.eesp.conv_1x1_exp.conv.weight, self.eesp.k, ep, out=(out, self.nin))
+            return out
         cat = self.eesp.reduce_transform(input)             # projection + K2 (do not need the reinforcement)
         join(0, (r,))
         scale, shift, rw = self._epilogue_vectors(r is not None)

@@ -291,6 +291,34 @@ def avgpool3x3s2(x, ep=None, out=None, plane_sums=False):
     return dst, sums
 
 
+def down_head_fits(shape, n, groups):
+    """True when a DownSampler's projection and pool run as one launch for an input of `shape` (N,nin,H,W)."""
+    N, nin, H, W = [int(v) for v in shape]
+    return bool(lib.mspl_down_head_fits(N, nin, int(n), int(groups), H, W, current_launch_flags()))
+
+
+def down_head(x, wproj, pscale, pshift, palpha, groups, ep, out):
+    """Head of a DownSampler block from one read of x (N,nin,H,W): returns (r, sums) with r (N,n,H,W) = PReLU(BN(grouped
+    1x1(x))) and sums (N*nin, nblk) the partial plane sums of x; channels [0, nin) of `out` (N,nout,H/2,W/2) receive the 3x3 / s2
+    average pool through ep (scale, shift, alpha over all nout channels, optionally the reinforcement)."""
+    x, wproj = _f32(x, 'x'), _f32(wproj, 'projection weight')
+    N, nin, H, W = x.shape
+    n = wproj.shape[0]
+    if wproj.numel() != n * (nin // groups) or nin % groups or n % groups:
+        raise RuntimeError('mspl_amd: down_head weight %s does not match nin=%d groups=%d' % (tuple(wproj.shape), nin, groups))
+    ps, pb, pa = _vec(pscale, n, 'pscale'), _vec(pshift, n, 'pshift'), _vec(palpha, n, 'palpha')
+    dst, coff = _dest((out, 0), (N, nin, H // 2, W // 2), x)
+    s, keep = _build(ep, dst, coff, N, nin, (H // 2) * (W // 2))
+    nblk = lib.mspl_down_head_psum_blocks(H, W)
+    if nblk <= 0:
+        check(nblk)
+    r = torch.empty((N, n, H, W), device=x.device, dtype=torch.float32)
+    sums = torch.empty((N * nin, nblk), device=x.device, dtype=torch.float32)
+    check(lib.mspl_down_head_fwd(_p(x), _p(wproj), _p(ps), _p(pb), _p(pa), N, nin, n, int(groups), H, W, ctypes.byref(s), _p(r),
+                                 _p(dst), _p(sums), _stream()))
+    return r, sums
+
+
 def gate_from_sums(plane_sums, w, hw):
     """sigmoid(W . sum_j plane_sums[:, j] / hw) -> (N, Cout): gap_gate without re-reading the tensor."""
     w = _f32(w, 'w')
