@@ -465,6 +465,19 @@ int mspl_uw_loss_heads_supported(int32_t C);
 int mspl_uw_loss_heads_fwd_bwd(const float* main_lo, const float* aux_lo, const int64_t* target, const float* class_weights,
                                int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
                                float ce_scale, float out_scale, float* loss_acc, float* gpred, float* gaux, void* stream);
+/* The same step with the training loop's meters taken inside the kernel (uest_seg_multi_os.py:1032-1037: `miou_class.get_iou(pred,
+ * labels)` with its two device-to-host copies, and `losses.update(loss.item(), images.size(0))`):
+ *   areas[3 * miou_classes] (64-bit counters, [inter | pred | mask]) += the three histograms of utilities/metrics/
+ *     segmentation_miou.py:28-41 for the first maximum of the up-sampled MAIN head against target, in the reference's uint8
+ *     arithmetic -- what mspl_miou_areas_fwd gives on mspl_bilinear_fwd(main_lo); values outside 1..miou_classes count nowhere
+ *     (the loop passes 4 for a 5-class model);
+ *   meter[0] (double) += meter_weight * loss (pass the step's batch size; a lane of a step passes it with out_scale = 1 / lanes).
+ * Both are ACCUMULATED into (caller zeroes).  Loss and gradients are those of mspl_uw_loss_heads_fwd_bwd; same support rule, plus
+ * 1 <= miou_classes <= 64. */
+int mspl_uw_loss_heads_meters_fwd_bwd(const float* main_lo, const float* aux_lo, const int64_t* target, const float* class_weights,
+                                      int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
+                                      float ce_scale, float out_scale, float* loss_acc, float* gpred, float* gaux,
+                                      int32_t miou_classes, float meter_weight, unsigned long long* areas, double* meter, void* stream);
 
 /* K13  dense (groups = 1) 1x1 / dilated 3x3 convolution on the fp32 matrix cores: the ASPP heads of nn_layers/aspp.py:7-99
  *      (Conv2d(Cin, Cout, k, padding = dilation, dilation) + BatchNorm + ReLU).  x: (N,Cin,H,W); w_packed: the conv weight

@@ -1152,7 +1152,7 @@ class UWLossHeadsFn(torch.autograd.Function):
     the node keeps two low-resolution tensors: three launches instead of five."""
 
     @staticmethod
-    def forward(ctx, main, aux, target, class_weights, ce_scale, out_scale, root):
+    def forward(ctx, main, aux, target, class_weights, ce_scale, out_scale, root, meters=None):
         main, aux = _c(main), _c(aux)
         N, C, Hm, Wm = main.shape
         Ha, Wa = aux.shape[2:]
@@ -1160,8 +1160,15 @@ class UWLossHeadsFn(torch.autograd.Function):
         target = _c(target.to(torch.int64))
         loss = torch.zeros(1, device=main.device, dtype=torch.float32)
         gfull = torch.empty((2, N, C, H, W), device=main.device, dtype=torch.float32)
-        check(lib.mspl_uw_loss_heads_fwd_bwd(_p(main), _p(aux), _p(target), _p(_c(class_weights.float())), N, C, Hm, Wm, Ha, Wa, H, W,
-                                             float(ce_scale), float(out_scale), _p(loss), _p(gfull[0]), _p(gfull[1]), _stream()))
+        if meters is None:
+            check(lib.mspl_uw_loss_heads_fwd_bwd(_p(main), _p(aux), _p(target), _p(_c(class_weights.float())), N, C, Hm, Wm, Ha, Wa, H, W,
+                                                 float(ce_scale), float(out_scale), _p(loss), _p(gfull[0]), _p(gfull[1]), _stream()))
+        else:
+            # the training loop's meters from the same launch; a lane (out_scale = 1 / lanes) weighs its share with the step's batch
+            check(lib.mspl_uw_loss_heads_meters_fwd_bwd(_p(main), _p(aux), _p(target), _p(_c(class_weights.float())), N, C, Hm, Wm, Ha, Wa,
+                                                        H, W, float(ce_scale), float(out_scale), _p(loss), _p(gfull[0]), _p(gfull[1]),
+                                                        int(meters.classes), float(N / out_scale), _p(meters.areas), _p(meters.meter),
+                                                        _stream()))
         gmain, gaux = torch.empty_like(main), torch.empty_like(aux)
         check(lib.mspl_bilinear_bwd(_p(gfull[0]), N, C, Hm, Wm, H, W, _p(gmain), _stream()))
         check(lib.mspl_bilinear_bwd(_p(gfull[1]), N, C, Ha, Wa, H, W, _p(gaux), _stream()))
@@ -1173,8 +1180,8 @@ class UWLossHeadsFn(torch.autograd.Function):
     def backward(ctx, g):
         gmain, gaux = ctx.saved_tensors
         if ctx.root:
-            return gmain, gaux, None, None, None, None, None
-        return gmain * g, gaux * g, None, None, None, None, None
+            return gmain, gaux, None, None, None, None, None, None
+        return gmain * g, gaux * g, None, None, None, None, None, None
 
 
 # functional spellings
@@ -1424,6 +1431,8 @@ def uw_loss_heads_supported(classes):
     return bool(lib.mspl_uw_loss_heads_supported(int(classes)))
 
 
-def uw_loss_heads(main, aux, target, class_weights, ce_scale=20.0, out_scale=1.0, root=False):
-    """uw_loss(bilinear(main, target.shape[-2:]), bilinear(aux, ...), ...) from the low-resolution heads."""
-    return UWLossHeadsFn.apply(main, aux, target, class_weights, ce_scale, out_scale, root)
+def uw_loss_heads(main, aux, target, class_weights, ce_scale=20.0, out_scale=1.0, root=False, meters=None):
+    """uw_loss(bilinear(main, target.shape[-2:]), bilinear(aux, ...), ...) from the low-resolution heads.  meters: an object with
+    `classes`, `areas` (int64[3 * classes]) and `meter` (float64[2]) on the device, e.g. training.TrainMeters: the same launch adds
+    MIOU(classes)'s three area histograms of the up-sampled main head and loss * batch size into them."""
+    return UWLossHeadsFn.apply(main, aux, target, class_weights, ce_scale, out_scale, root, meters)

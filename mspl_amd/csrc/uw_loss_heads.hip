@@ -38,12 +38,32 @@ __device__ __forceinline__ float uh_log(float x) { return __logf(x); }
 
 // CM: class capacity of the register arrays; EXACT: C == CM (no per-class predicates).  Up to 8 classes the three exponentials of a
 // class are kept from the sums to the gradients; beyond, they are recomputed (5 x CM registers spill at CM = 20).
-template <int CM, bool EXACT>
+//
+// METERS: the training loop's per-step meters (uest_seg_multi_os.py:1032-1037) taken where the up-sampled main logits already sit in
+// registers.  MIOU(K).get_iou(pred, labels) is the first maximum of a[0..C) (torch.max(output, 1) on the MAIN head alone, not on
+// a + 0.5 bv) and uint8 arithmetic on it (segmentation_miou.py:28-41, the rule of miou_areas_kernel in labels.hip); the pixel's
+// two codes p and g ride through the four pixels of a row packed in two registers, and the three K-bin histograms are taken per
+// row after the pixel loop: a compare per bin, the population count of its lane mask on the scalar unit, one LDS add by lane 0
+// (label_epilogue's histogram, labels.hip).  Per workgroup: one 64-bit atomic per non-empty bin, and one double atomic that adds
+// meter_weight x (its share of the loss) for losses.update(loss.item(), images.size(0)).  The non-METERS instantiations compile to
+// what they were before the meters existed (every addition sits under `if constexpr`-like constant conditions).
+struct UhMeters {
+    unsigned long long* areas;      // [3 K]: inter | pred | mask
+    double* meter;                  // meter[0] += meter_weight * loss
+    int K;
+    float weight;
+};
+
+template <int CM, bool EXACT, bool METERS = false>
 __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restrict__ mainp, const float* __restrict__ auxp,
                                                             const int64_t* __restrict__ target, const float* __restrict__ cw,
                                                             UhGeom g, float* __restrict__ loss_acc, float* __restrict__ gpred,
-                                                            float* __restrict__ gaux) {
+                                                            float* __restrict__ gaux, UhMeters mt) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ unsigned int mhist[METERS ? 3 * 64 : 1];
+    if (METERS) {
+        for (int i = threadIdx.x; i < 3 * mt.K; i += 256) mhist[i] = 0;       // (ordered before its first use by the tile loop's barrier)
+    }
     const int C = EXACT ? CM : g.C;
     constexpr bool KEEP = CM <= 8;
     constexpr int CK = KEEP ? CM : 1;
@@ -90,6 +110,7 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
             const size_t goff = ((size_t)img * C * g.H + y) * (size_t)g.W;
             // a wave takes the row's 256 columns as four runs of 64 (coalesced label loads and gradient stores), one pixel per lane
             // at a time: unrolled, the four pixels' softmax terms are all live at once (205 VGPRs at C = 5, spills beyond)
+            unsigned pk_p = 0, pk_g = 0;     // METERS: the row's four (p, g) codes, a byte each; 0 counts nowhere
 #pragma unroll 1
             for (int j = 0; j < 4; ++j) {
                 const int xs = x0 + j * 64 + lane;
@@ -113,6 +134,16 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
                         bv[c] = wy0a * topa + wy1a * bota;
                         m1 = fmaxf(m1, a[c]);  m2 = fmaxf(m2, bv[c]);  mo = fmaxf(mo, a[c] + 0.5f * bv[c]);
                     }
+                }
+                if (METERS) {
+                    float best = a[0];  unsigned bi = 0;
+#pragma unroll
+                    for (int c = 1; c < CM; ++c)
+                        if ((EXACT || c < C) && a[c] > best) { best = a[c];  bi = (unsigned)c; }
+                    const unsigned g8 = ((unsigned)(t & 255) + 1u) & 255u;
+                    const unsigned p8 = g8 ? bi + 1u : 0u;
+                    pk_p |= p8 << (8 * j);
+                    pk_g |= g8 << (8 * j);
                 }
                 float e1[CK], e2[CK], eo[CK];
                 float s1 = 0.f, s2 = 0.f, so = 0.f;
@@ -158,6 +189,24 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
                     }
                 }
             }
+            if (METERS) {
+                const unsigned eq = pk_p ^ pk_g;                        // a zero byte: p == g, the intersection carries p
+                for (unsigned k = 1; k <= (unsigned)mt.K; ++k) {
+                    unsigned ci = 0, cp = 0, cg = 0;                     // wave-uniform
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const bool isp = ((pk_p >> (8 * j)) & 0xffu) == k, isg = ((pk_g >> (8 * j)) & 0xffu) == k;
+                        cp += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(isp));
+                        cg += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(isg));
+                        ci += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(isp && ((eq >> (8 * j)) & 0xffu) == 0u));
+                    }
+                    if (lane == 0) {
+                        if (ci) atomicAdd(&mhist[k - 1], ci);
+                        if (cp) atomicAdd(&mhist[mt.K + k - 1], cp);
+                        if (cg) atomicAdd(&mhist[2 * mt.K + k - 1], cg);
+                    }
+                }
+            }
         }
         __syncthreads();                 // the next tile's staging overwrites the patches
     }
@@ -166,7 +215,18 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
     __shared__ float part[4];
     if (lane == 0) part[wave] = contrib;
     __syncthreads();
-    if (tid == 0) atomicAdd(loss_acc, (part[0] + part[1]) + (part[2] + part[3]));
+    if (!METERS) {
+        if (tid == 0) atomicAdd(loss_acc, (part[0] + part[1]) + (part[2] + part[3]));
+    } else {
+        if (tid == 0) {
+            const float share = (part[0] + part[1]) + (part[2] + part[3]);
+            atomicAdd(loss_acc, share);
+            atomicAdd(mt.meter, (double)mt.weight * (double)share);
+        }
+        // (the tile loop's last barrier ordered every wave's LDS adds; a workgroup with no tile has only zeros)
+        for (int i = tid; i < 3 * mt.K; i += 256)
+            if (mhist[i]) atomicAdd(&mt.areas[i], (unsigned long long)mhist[i]);
+    }
 }
 
 // The device's source rule on the host (one fp32 product, floor, clamp: the same values), for exact patch sizes.
@@ -196,9 +256,12 @@ using namespace mspl;
 // (a predicated 20-class form for the counts in between spills 6 600 registers: those take the three-step form)
 extern "C" int mspl_uw_loss_heads_supported(int32_t C) { return (C >= 1 && C <= 8) || C == 13 || C == 20; }
 
-extern "C" int mspl_uw_loss_heads_fwd_bwd(const float* main_lo, const float* aux_lo, const int64_t* target, const float* class_weights,
-                                          int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
-                                          float ce_scale, float out_scale, float* loss_acc, float* gpred, float* gaux, void* stream) {
+// mt == nullptr: the plain kernel.  With meters the workgroup's 3 x 64 LDS counters come on top of the patches, so the band is sized
+// against 1 KB less (the gradients of a pixel do not depend on the band it falls in).
+static int uh_launch(const float* main_lo, const float* aux_lo, const int64_t* target, const float* class_weights,
+                     int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
+                     float ce_scale, float out_scale, float* loss_acc, float* gpred, float* gaux, const UhMeters* mt, void* stream) {
+    const size_t extra = mt ? 1024 : 0;
     MSPL_REQUIRE(main_lo && aux_lo && target && class_weights && loss_acc && gpred && gaux, MSPL_ERR_NULL_POINTER, "uw_loss_heads: null pointer");
     MSPL_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && Hm > 0 && Wm > 0 && Ha > 0 && Wa > 0, MSPL_ERR_BAD_SHAPE,
                  "uw_loss_heads: bad shape N=%d C=%d main %dx%d aux %dx%d labels %dx%d", N, C, Hm, Wm, Ha, Wa, H, W);
@@ -219,7 +282,7 @@ extern "C" int mspl_uw_loss_heads_fwd_bwd(const float* main_lo, const float* aux
         lds = (size_t)C * ((size_t)g.MR * g.MC + (size_t)g.AR * g.AC) * sizeof(float);
     };
     int th = ((int64_t)N * ceil_div(H, 8) * g.tiles_x >= 768) ? 8 : 4;
-    for (size_for(th); lds > 64 * 1024 && th > 1; size_for(th)) th >>= 1;
+    for (size_for(th); lds + extra > 64 * 1024 && th > 1; size_for(th)) th >>= 1;
     MSPL_REQUIRE(lds <= 128 * 1024, MSPL_ERR_UNSUPPORTED, "uw_loss_heads: patches of %zu bytes do not fit", lds);
     g.tiles_y = ceil_div(H, g.TH);
     const int64_t tiles = (int64_t)N * g.tiles_y * g.tiles_x;
@@ -234,10 +297,17 @@ extern "C" int mspl_uw_loss_heads_fwd_bwd(const float* main_lo, const float* aux
     static bool attr_ok = false;
     std::call_once(once, [] {
         attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&uw_loss_heads_kernel<13, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess &&
-                  hipFuncSetAttribute(reinterpret_cast<const void*>(&uw_loss_heads_kernel<20, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;
+                  hipFuncSetAttribute(reinterpret_cast<const void*>(&uw_loss_heads_kernel<20, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess &&
+                  hipFuncSetAttribute(reinterpret_cast<const void*>(&uw_loss_heads_kernel<13, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess &&
+                  hipFuncSetAttribute(reinterpret_cast<const void*>(&uw_loss_heads_kernel<20, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;
     });
-    MSPL_REQUIRE(lds <= 64 * 1024 || (attr_ok && C > 8), MSPL_ERR_UNSUPPORTED, "uw_loss_heads: patches of %zu bytes do not fit", lds);
-#define MSPL_UH(CMv, EX) hipLaunchKernelGGL((uw_loss_heads_kernel<CMv, EX>), dim3(blocks), dim3(256), lds, s, main_lo, aux_lo, target, class_weights, g, loss_acc, gpred, gaux)
+    MSPL_REQUIRE(lds + extra <= 64 * 1024 || (attr_ok && C > 8), MSPL_ERR_UNSUPPORTED, "uw_loss_heads: patches of %zu bytes do not fit", lds);
+    const UhMeters m = mt ? *mt : UhMeters{nullptr, nullptr, 0, 0.f};
+#define MSPL_UH(CMv, EX)                                                                                                                       \
+    do {                                                                                                                                       \
+        if (mt) hipLaunchKernelGGL((uw_loss_heads_kernel<CMv, EX, true>), dim3(blocks), dim3(256), lds, s, main_lo, aux_lo, target, class_weights, g, loss_acc, gpred, gaux, m); \
+        else hipLaunchKernelGGL((uw_loss_heads_kernel<CMv, EX, false>), dim3(blocks), dim3(256), lds, s, main_lo, aux_lo, target, class_weights, g, loss_acc, gpred, gaux, m); \
+    } while (0)
     if (C == 5) MSPL_UH(5, true);
     else if (C <= 8) MSPL_UH(8, false);
     else if (C == 13) MSPL_UH(13, true);
@@ -245,4 +315,23 @@ extern "C" int mspl_uw_loss_heads_fwd_bwd(const float* main_lo, const float* aux
 #undef MSPL_UH
     MSPL_CHECK_LAUNCH("uw_loss_heads");
     return MSPL_OK;
+}
+
+extern "C" int mspl_uw_loss_heads_fwd_bwd(const float* main_lo, const float* aux_lo, const int64_t* target, const float* class_weights,
+                                          int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
+                                          float ce_scale, float out_scale, float* loss_acc, float* gpred, float* gaux, void* stream) {
+    return uh_launch(main_lo, aux_lo, target, class_weights, N, C, Hm, Wm, Ha, Wa, H, W, ce_scale, out_scale, loss_acc, gpred, gaux, nullptr, stream);
+}
+
+// The same step with the training loop's meters (uest_seg_multi_os.py:1032-1037) taken inside the kernel: areas[3 K] += the
+// [inter | pred | mask] histograms of MIOU(miou_classes).get_iou(up-sampled main head, target), meter[0] += meter_weight * loss.
+// Both are accumulated into: the caller zeroes them.
+extern "C" int mspl_uw_loss_heads_meters_fwd_bwd(const float* main_lo, const float* aux_lo, const int64_t* target, const float* class_weights,
+                                                 int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
+                                                 float ce_scale, float out_scale, float* loss_acc, float* gpred, float* gaux,
+                                                 int32_t miou_classes, float meter_weight, unsigned long long* areas, double* meter, void* stream) {
+    MSPL_REQUIRE(areas && meter, MSPL_ERR_NULL_POINTER, "uw_loss_heads_meters: null pointer");
+    MSPL_REQUIRE(miou_classes >= 1 && miou_classes <= 64, MSPL_ERR_UNSUPPORTED, "uw_loss_heads_meters: %d classes (1..64)", miou_classes);
+    const UhMeters mt{areas, meter, miou_classes, meter_weight};
+    return uh_launch(main_lo, aux_lo, target, class_weights, N, C, Hm, Wm, Ha, Wa, H, W, ce_scale, out_scale, loss_acc, gpred, gaux, &mt, stream);
 }

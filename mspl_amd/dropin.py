@@ -89,11 +89,12 @@ def _alias(name, **attrs):
     return mod
 
 
-def install_dropin(force=False, script=None):
+def install_dropin(force=False, script=None, train_loops=False):
     """Register the alias modules.  Refuses to shadow already-imported reference modules unless force=True.
     script: the globals() (or module object) of uest_seg_multi_os.py -- the functions the script defines itself (get_output,
     merge_outputs, update_image_list, generate_pseudo_label, generate_pseudo_label_multi_model) are rebound there too
-    (mspl_amd.script.patch_script; call after the script's own definitions)."""
+    (mspl_amd.script.patch_script; call after the script's own definitions).  train_loops=True also rebinds the script's `train`
+    to the loop on the graphed training step (mspl_amd.script.train)."""
     from . import layers as L, models as M, uest as U
     names = ['nn_layers', 'model', 'loss_fns']
     if not force:
@@ -136,4 +137,4 @@ def install_dropin(force=False, script=None):
            SegmentationLoss=S.SegmentationLoss, NIDLoss=S.NIDLoss)
     if script is not None:
         from .script import patch_script
-        patch_script(script)
+        patch_script(script, train=train_loops)

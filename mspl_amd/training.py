@@ -39,21 +39,71 @@ def uest_loss(pred, aux, labels, class_weights, ignore_idx=None, ce_scale=20.0):
 _LOSS_AT_HEADS = os.environ.get('MSPL_LOSS_HEADS', '1') != '0'      # A/B aid: 0 = up-sample both heads, then the loss
 
 
-def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=False):
+class TrainMeters:
+    """The per-epoch meters of the reference's train() (uest_seg_multi_os.py:964-969, 1032-1037, 1050) kept on the device:
+    `areas` int64[3 K] = [inter | pred | mask] summed over the steps (MIOU(num_classes=K).get_iou on the main head), `meter`
+    float64[2] = [sum of loss * batch size, sum of the additional loss].  The loss kernel adds into both (forward_loss(...,
+    meters=...)); the step and image counts are host integers.  `read()` is the one device-to-host copy and sync of an epoch.
+
+    The sums are integers, where the reference sums float32 arrays (AverageMeter over numpy float32 histograms, which stop counting
+    exactly past 2^24 pixels per class): a deliberate difference, invisible below that count."""
+
+    def __init__(self, classes=4, device='cuda'):
+        self.classes = int(classes)
+        self.areas = torch.zeros(3 * self.classes, dtype=torch.int64, device=device)
+        self.meter = torch.zeros(2, dtype=torch.float64, device=device)
+        self.steps = 0
+        self.images = 0
+
+    def reset(self):
+        self.areas.zero_()
+        self.meter.zero_()
+        self.steps = 0
+        self.images = 0
+
+    def count(self, batch_size):
+        """One step of `batch_size` images went in (host side; the device sums are added by the kernels)."""
+        self.steps += 1
+        self.images += int(batch_size)
+
+    def add(self, pred, labels, loss, batch_size, extra=None):
+        """The same sums from a full-size main head and a loss tensor (the forms the heads kernel does not cover): the integer area
+        kernel and device-side adds, no sync."""
+        from .metrics import MIOU
+        self.areas += MIOU(self.classes).areas(pred.detach(), labels).reshape(-1)
+        self.meter[0] += loss.detach().double() * float(batch_size)
+        if extra is not None:
+            self.meter[1] += extra.detach().double()
+
+    def read(self):
+        """{'loss_avg', 'extra_sum', 'inter' [K], 'union' [K], 'steps'}: union = pred + mask - inter + steps * 1e-6 (the reference adds
+        its epsilon once per step, segmentation_miou.py:41)."""
+        import numpy as np
+        a = self.areas.cpu().numpy().reshape(3, self.classes).astype(np.float64)       # (synchronises)
+        m = self.meter.cpu().numpy()
+        return {'loss_avg': float(m[0]) / max(1, self.images), 'extra_sum': float(m[1]), 'inter': a[0],
+                'union': a[1] + a[2] - a[0] + self.steps * 1e-6, 'areas': a, 'steps': self.steps}
+
+
+def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=False, meters=None):
     """model forward + uest loss (uest_seg_multi_os.py:1010-1023) on device class weights `cw`.  A model that exposes its decoder
     outputs (`forward_lowres`: main at H/2, auxiliary at H/4) gets the loss taken at head resolution -- the up-sampling of
     espdnet_ue.py:301-302 happens inside the loss kernel (ag.uw_loss_heads), same value and gradients; any other model is called as
-    the reference calls it and the loss takes its two full-size outputs."""
+    the reference calls it and the loss takes its two full-size outputs.  meters: a TrainMeters that receives this batch's area
+    histograms and loss * batch size (a lane passes out_scale = 1 / lanes and adds its share)."""
     lowres = getattr(model, 'forward_lowres', None) if _LOSS_AT_HEADS else None
     if lowres is not None:
         main, aux = lowres(images)
         if aux is not None and ag.uw_loss_heads_supported(main.shape[1]):
-            return ag.uw_loss_heads(main, aux, labels, cw, ce_scale, out_scale, root)
+            return ag.uw_loss_heads(main, aux, labels, cw, ce_scale, out_scale, root, meters)
         size = tuple(images.shape[2:])
         pred, aux = ag.bilinear(main, size), ag.bilinear(aux, size)
     else:
         pred, aux = model(images)
-    return ag.uw_loss(pred, aux, labels, cw, ce_scale, out_scale, root)
+    loss = ag.uw_loss(pred, aux, labels, cw, ce_scale, out_scale, root)
+    if meters is not None:      # the three-step form: the existing area kernel on the full-size main head, loss * B added on the device
+        meters.add(pred, labels, loss, images.shape[0] / out_scale)
+    return loss
 
 
 class FlatAdam:
@@ -112,16 +162,19 @@ def adjust_learning_rate(optimizer, i_iter, tot_iter, base_lr, power=0.0):
 
 
 def train_step(model, images, labels, class_weights, optimizer=None, ignore_idx=None, lr=5e-4, weight_decay=5e-4,
-               ce_scale=20.0):
+               ce_scale=20.0, meters=None):
     """One optimisation step; returns (loss tensor, optimizer).  Pass optimizer=None on the first call: it is built
-    after the first backward (which reveals the gradient-bearing parameters)."""
+    after the first backward (which reveals the gradient-bearing parameters).  meters: a TrainMeters the step is added to."""
     if optimizer is not None:
         optimizer.zero_grad()
     tr = getattr(optimizer, 'transposer', None)
     with torch.enable_grad(), ag.grad_sinks(), (tr.active() if tr is not None else ag.collect_conv_weights()) as got:
         layers.prefold_frozen_bn(model)
-        loss = forward_loss(model, images, labels, _device_class_weights(class_weights, images.device, ignore_idx), ce_scale)
+        loss = forward_loss(model, images, labels, _device_class_weights(class_weights, images.device, ignore_idx), ce_scale,
+                            meters=meters)
         loss.backward()
+    if meters is not None:
+        meters.count(images.shape[0])
     if optimizer is None:
         optimizer = FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay)
         # (built after FlatAdam: the parameters now live in its flat buffer)
@@ -165,8 +218,16 @@ class GraphedTrainStep:
     The first call runs one eager step (it reveals the gradient-bearing parameters and builds FlatAdam) and captures;
     later calls copy the batch into static buffers and replay.  Shapes are fixed at construction."""
 
-    def __init__(self, model, images, labels, class_weights, ignore_idx=None, lr=5e-4, weight_decay=5e-4, ce_scale=20.0, lanes=1):
+    def __init__(self, model, images, labels, class_weights, ignore_idx=None, lr=5e-4, weight_decay=5e-4, ce_scale=20.0, lanes=1,
+                 meters=None, consume_first_batch=True):
+        """meters: a TrainMeters captured inside the graph(s) -- every lane adds into the same buffers; it is reset when the
+        constructor returns.  consume_first_batch=False: the construction batch only shapes the capture -- the parameters are put
+        back to their values on entry, both Adam moments, the step count and the meters are zeroed, so the first call is step 1 (a
+        training loop applies each batch exactly once; the default applies the construction batch twice: an eager step, then the
+        captured one)."""
         self.model = model
+        self.meters = meters
+        entry = None if consume_first_batch else [p.detach().clone() for p in model.parameters()]
         self.images = images.detach().clone()
         self.labels = labels.detach().to(torch.int64).clone()
         self.cw = _device_class_weights(class_weights, images.device, ignore_idx)
@@ -183,7 +244,7 @@ class GraphedTrainStep:
                 self.optimizer.zero_grad()
                 with torch.enable_grad(), ag.grad_sinks(), tr.active():
                     layers.prefold_frozen_bn(model)
-                    self.loss = forward_loss(model, self.images, self.labels, self.cw, ce_scale, root=True)
+                    self.loss = forward_loss(model, self.images, self.labels, self.cw, ce_scale, root=True, meters=meters)
                     self.loss.backward()
         else:
             # what every lane needs first: zeroed gradients, this step's transposed weights and folded BatchNorms (their tensors live
@@ -211,7 +272,7 @@ class GraphedTrainStep:
                     with torch.cuda.graph(g, stream=st):
                         with torch.enable_grad(), ag.grad_sinks(), tr.active(refresh=False):
                             loss = forward_loss(model, self.images[i * b:(i + 1) * b], self.labels[i * b:(i + 1) * b], self.cw, ce_scale,
-                                                out_scale=1.0 / self.lanes, root=True)
+                                                out_scale=1.0 / self.lanes, root=True, meters=meters)
                             loss.backward()
                     self.lane_graphs.append(g)
                     self.lane_losses.append(loss)
@@ -227,6 +288,36 @@ class GraphedTrainStep:
             self.graph.replay()
             self._settle_streams()
         self._finish()      # run the step the capture recorded
+        if entry is not None:
+            with torch.no_grad():
+                for p, p0 in zip(model.parameters(), entry):      # (.data are views of the flat buffer by now: written in place)
+                    p.copy_(p0)
+            self.optimizer.m.zero_()
+            self.optimizer.v.zero_()
+            self.optimizer.step_count = 0
+            layers.bump_param_epoch()
+        if meters is not None:
+            meters.reset()
+
+    def set_class_weights(self, class_weights, ignore_idx=None):
+        """New class weights (a relabelling round, uest_seg_multi_os.py:527-530): copied into the tensor the graphs read."""
+        self.cw.copy_(_device_class_weights(class_weights, self.cw.device, ignore_idx))
+
+    def reset_optimizer(self, lr=None, betas=None, eps=None, weight_decay=None):
+        """Start over as a fresh torch.optim.Adam would: zero moments and step count (the script builds a new optimizer per round,
+        :594-598); hyper-parameters given are taken over."""
+        opt = self.optimizer
+        opt.m.zero_()
+        opt.v.zero_()
+        opt.step_count = 0
+        if lr is not None:
+            opt.lr = lr
+        if betas is not None:
+            opt.betas = tuple(betas)
+        if eps is not None:
+            opt.eps = eps
+        if weight_decay is not None:
+            opt.weight_decay = weight_decay
 
     def _lanes_ms(self, streams, reps=2):
         """Wall time of one replay of every lane graph, lane i on streams[i % len(streams)] (the gradients they add up are thrown away by
@@ -289,6 +380,8 @@ class GraphedTrainStep:
             self.loss = torch.stack([l.detach() for l in self.lane_losses]).sum()
         self.optimizer.all_reduce_grads()
         self.optimizer.step()
+        if self.meters is not None:
+            self.meters.count(self.images.shape[0])
         return self.loss.detach()
 
     def __call__(self, images, labels):
