@@ -79,7 +79,8 @@ typedef struct {
 #define MSPL_LAUNCH_K2_STREAM_FORCE 4u
 
 const char* mspl_version(void);
-/* ABI revision of this library; it changes whenever a struct layout or a signature in this header does.  3 = this header. */
+/* ABI revision of this library; it changes whenever a struct layout or a signature in this header does.  4 = this header
+ * (mspl_adam_step takes its betas as doubles). */
 int mspl_abi_version(void);
 /* Copies the calling thread's last error text (NUL-terminated) into buf; returns its length. */
 size_t mspl_last_error(char* buf, size_t cap);
@@ -691,8 +692,10 @@ int mspl_sum_n_planes(const float* const* srcs, int32_t n, const float* plane_co
  * element} -- one workgroup of 256 destination elements each. */
 int mspl_transpose_weights(const void* seg_table, const void* block_table, int32_t nblocks, void* stream);
 
-/* torch.optim.Adam step on a flat fp32 buffer (L2 weight decay folded into the gradient; bias correction by `step`). */
-int mspl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+/* torch.optim.Adam step on a flat fp32 buffer (L2 weight decay folded into the gradient; bias correction by `step`).  The betas
+ * are doubles: 1 - beta and 1 - beta^step are formed in double on the host, as torch forms them (1 - (float)0.999 is off by
+ * 1.3e-5 of itself, which would scale every second moment). */
+int mspl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
                    float eps, float weight_decay, int32_t step, void* stream);
 
 /* ---- train-time loader transforms ------------------------------------------------------------------------------------

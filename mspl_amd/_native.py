@@ -42,7 +42,7 @@ class TrainRec(ctypes.Structure):
 FILTER_LANCZOS = 1              # MSPL_FILTER_LANCZOS
 FILTER_BILINEAR = 2             # MSPL_FILTER_BILINEAR
 
-ABI_VERSION = 3                 # include/mspl_hip.h: mspl_abi_version()
+ABI_VERSION = 4                 # include/mspl_hip.h: mspl_abi_version()
 ERR_UNSUPPORTED = -2            # MSPL_ERR_UNSUPPORTED
 LAUNCH_THROUGHPUT = 1           # MSPL_LAUNCH_THROUGHPUT
 LAUNCH_K2_STREAM_OFF = 2        # MSPL_LAUNCH_K2_STREAM_OFF
@@ -184,7 +184,8 @@ SIGNATURES = {
     'mspl_sum_n': [ctypes.POINTER(ctypes.c_void_p), c_i32, c_i64, c_f32p, ctypes.c_void_p],
     'mspl_sum_n_planes': [ctypes.POINTER(ctypes.c_void_p), c_i32, c_f32p, ctypes.c_float, c_i32, c_i32, c_f32p, ctypes.c_void_p],
     'mspl_transpose_weights': [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p],
-    'mspl_adam_step': [c_f32p, c_f32p, c_f32p, c_f32p, c_i64] + [ctypes.c_float] * 5 + [c_i32, ctypes.c_void_p],
+    'mspl_adam_step': [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_float, ctypes.c_float,
+                       c_i32, ctypes.c_void_p],
     'mspl_merge_labels_fwd': [ctypes.POINTER(ctypes.c_void_p), c_i32, c_i64, c_i32, c_i32, c_i32, ctypes.c_void_p,
                               ctypes.c_void_p, ctypes.c_void_p],
 }

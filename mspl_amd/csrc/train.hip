@@ -1013,13 +1013,13 @@ __global__ __launch_bounds__(256) void uw_loss_kernel(const float* __restrict__ 
 
 // ---- Adam (torch.optim.Adam semantics: L2 weight decay folded into the gradient, bias correction)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
-                                                   float wd, float bc1, float bc2_sqrt) {
+                                                   float* __restrict__ v, int64_t n, float lr, float b1, float b2, float omb1,
+                                                   float omb2, float eps, float wd, float bc1, float bc2_sqrt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float gi = g[i] + wd * p[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;          // omb = 1 - beta rounded from double (torch's `value=1 - beta2`)
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     p[i] -= (lr / bc1) * (mi / denom);
@@ -1625,15 +1625,17 @@ extern "C" int mspl_uw_loss_scaled_fwd_bwd(const float* pred, const float* aux, 
     return uw_loss_launch(pred, aux, target, class_weights, N, C, HW, ce_scale, out_scale, loss_acc, gpred, gaux, kld_out, stream);
 }
 
-extern "C" int mspl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+extern "C" int mspl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
                               float eps, float weight_decay, int32_t step, void* stream) {
     MSPL_REQUIRE(p && g && m && v, MSPL_ERR_NULL_POINTER, "adam_step: null pointer");
     MSPL_REQUIRE(n >= 0 && step >= 1, MSPL_ERR_BAD_SHAPE, "adam_step: n=%lld step=%d", (long long)n, step);
     if (n == 0) return MSPL_OK;
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                       beta2, eps, weight_decay, bc1, bc2s);
+    // in double, as torch.optim.Adam forms them: (float)0.999 is 1.3e-8 too large, which 1.f - beta2 turns into 1.3e-5 of every second
+    // moment and powf(beta2, step) into 1.3e-8 * step of the bias correction (tests/optim_shadow.py)
+    const float bc1 = (float)(1.0 - pow(beta1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
+                       (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, bc1, bc2s);
     MSPL_CHECK_LAUNCH("adam_step");
     return MSPL_OK;
 }

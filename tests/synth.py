@@ -171,7 +171,16 @@ def assert_weights_close_after_adam(got, want, lr, steps, tight=5e-5, frac=0.01)
     that noise, and an ulp of difference in a weight can put one PReLU input of a tiny map on the other side of zero, which moves
     the gradients of that block by per cent (tools/diag_sinks.py).  So: every element within 2 * lr * steps, and all but `frac`
     of them within `tight` -- a missing, doubled or misplaced gradient moves far more than one per cent of the elements.
-    got / want: dicts of tensors (state_dicts), tensors or arrays."""
+    got / want: dicts of tensors (state_dicts), tensors or arrays.
+
+    What this can and cannot detect: it sees damage spread over more than `frac` of ALL elements taken together (a gradient missing
+    from a large layer, a step applied twice, a batch lost).  It cannot see a wrong update of a small tensor -- PReLU slopes,
+    BatchNorm gamma / beta, depthwise stage weights, one 1x1 layer are each far below one per cent of the 798 488 elements -- and
+    its first bound holds for ANY two Adam runs of that length, right or wrong (swapped betas, a stale moment, a lost wd * p all move
+    a weight by about lr per step, like the real thing).  Power per tensor comes from elsewhere: the gradient of every tensor is
+    checked against a float64 oracle (tests/test_gpu_grad_parity.py, tests/test_gpu_supervised_grad_parity.py), and the update
+    that follows it by the step audit (tests/optim_shadow.py StepAudit, installed in the tests that call this helper), which compares
+    every element of every optimizer step with the float64 formula at that step's own inputs."""
     import numpy as np
     import torch
 

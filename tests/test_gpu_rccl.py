@@ -81,6 +81,7 @@ def test_train_step_with_rccl_all_reduce_between_graph_and_adam(nccl_world1):
     before the Adam kernel, and the step equals the same step without a process group collective."""
     import argparse
     from mspl_amd import dist as md, models, training
+    from tests.optim_shadow import StepAudit
     from tests.synth import synth_input, synth_state_dict
 
     def build():
@@ -95,10 +96,13 @@ def test_train_step_with_rccl_all_reduce_between_graph_and_adam(nccl_world1):
     outs = []
     for forced in (False, True):
         m = build()
-        with (md.force_collectives() if forced else contextlib.nullcontext()):
+        with StepAudit(m) as audit, (md.force_collectives() if forced else contextlib.nullcontext()):
             step = training.GraphedTrainStep(m, x, y, cw, ignore_idx=4, lr=5e-4, weight_decay=5e-4)   # (its first, eager step too)
             losses = [float(step(x, y)) for _ in range(2)]
         outs.append((losses, step.optimizer.flat_p.detach().cpu().numpy()))
+        # Adam at the gradient the all-reduce left behind: every element of every tensor against float64, steps 1-4
+        audit.check(m, label='rccl world 1 forced=%s' % forced)
+        assert audit.steps == [(i + 1, [5e-4]) for i in range(4)]
     # float atomics order the gradient sums differently from run to run: same tolerances as test_micro_batch_lanes_equal_one_graph
     np.testing.assert_allclose(outs[1][0], outs[0][0], rtol=2e-4, atol=1e-6)
     from tests.synth import assert_weights_close_after_adam

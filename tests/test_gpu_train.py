@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from oracle import labels as olab
 from tests.cases import TRAIN_CASE, TRAIN_CASES
+from tests.optim_shadow import StepAudit
 from tests.synth import assert_weights_close_after_adam
 from tests.conftest import GOLDEN
 from tests.synth import synth_input, synth_labels, synth_state_dict
@@ -363,12 +364,16 @@ def test_second_step_and_train_step_helper():
     x = synth_input((2, 3, 32, 48), 8).to(DEV)
     y = synth_labels((2, 32, 48), 5, 8).to(DEV)
     cw = torch.ones(5)
-    l0, opt = training.train_step(m, x, y, cw, None, ignore_idx=4, lr=2e-3)
-    losses = [float(l0)]
-    for _ in range(5):
-        l, opt = training.train_step(m, x, y, cw, opt, ignore_idx=4)
-        losses.append(float(l))
+    with StepAudit(m) as audit:
+        l0, opt = training.train_step(m, x, y, cw, None, ignore_idx=4, lr=2e-3)
+        losses = [float(l0)]
+        for _ in range(5):
+            l, opt = training.train_step(m, x, y, cw, opt, ignore_idx=4)
+            losses.append(float(l))
     assert all(np.isfinite(losses)) and losses[-1] < losses[0], losses      # same batch: the loss must go down
+    # every one of the six Adam steps, every element of the 340 tensors, against float64 at that step's own inputs
+    audit.check(m, label='train_step helper')
+    assert audit.steps == [(i + 1, [2e-3]) for i in range(6)]
 
 
 def test_graphed_train_step_equals_eager():
@@ -383,15 +388,19 @@ def test_graphed_train_step_equals_eager():
         m = models.ESPDNetwithUncertaintyEstimation(a, classes=5, dataset='greenhouse', fix_pyr_plane_proj=True)
         m.load_state_dict(synth_state_dict(KEYS['espdnetue_s2.0_c5'], 3))
         nets.append(m.to(DEV).eval())
-    l, opt = training.train_step(nets[0], x, y, cw, None, ignore_idx=4)
-    eager = [float(l)]
-    for _ in range(3):
-        l, opt = training.train_step(nets[0], x, y, cw, opt, ignore_idx=4)
-        eager.append(float(l))
-    gs = training.GraphedTrainStep(nets[1], x, y, cw, ignore_idx=4)      # eager step 1 + captured step 2
-    graphed = [float(gs(x, y)) for _ in range(2)]
+    with StepAudit(*nets) as audit:
+        l, opt = training.train_step(nets[0], x, y, cw, None, ignore_idx=4)
+        eager = [float(l)]
+        for _ in range(3):
+            l, opt = training.train_step(nets[0], x, y, cw, opt, ignore_idx=4)
+            eager.append(float(l))
+        gs = training.GraphedTrainStep(nets[1], x, y, cw, ignore_idx=4)      # eager step 1 + captured step 2
+        graphed = [float(gs(x, y)) for _ in range(2)]
     np.testing.assert_allclose(graphed, eager[2:], rtol=2e-4, atol=1e-6)
     assert_weights_close_after_adam(nets[1].state_dict(), nets[0].state_dict(), lr=5e-4, steps=4)
+    for k, net in enumerate(nets):      # each run's own four steps, per tensor (what the cross-run comparison above cannot see)
+        audit.check(net, label='graphed=eager net %d' % k)
+        assert [(r.step, r.lrs) for r in audit.records_of(net)] == [(i + 1, [5e-4]) for i in range(4)]
 
 
 @pytest.mark.parametrize('lanes', [2, 4])
@@ -409,14 +418,18 @@ def test_micro_batch_lanes_equal_one_graph(lanes):
         m = models.ESPDNetwithUncertaintyEstimation(a, classes=5, dataset='greenhouse', fix_pyr_plane_proj=True)
         m.load_state_dict(synth_state_dict(KEYS['espdnetue_s2.0_c5'], 3))
         nets.append(m.to(DEV).eval())
-    one = training.GraphedTrainStep(nets[0], x, y, cw, ignore_idx=4)
-    many = training.GraphedTrainStep(nets[1], x, y, cw, ignore_idx=4, lanes=lanes)
-    assert many.lanes == lanes and len(many.lane_graphs) == lanes
-    np.testing.assert_allclose(many.optimizer.flat_g.cpu().numpy(), one.optimizer.flat_g.cpu().numpy(), rtol=1e-4, atol=1e-4)
-    l1 = [float(one(x, y)) for _ in range(2)]
-    l2 = [float(many(x, y)) for _ in range(2)]
+    with StepAudit(*nets) as audit:
+        one = training.GraphedTrainStep(nets[0], x, y, cw, ignore_idx=4)
+        many = training.GraphedTrainStep(nets[1], x, y, cw, ignore_idx=4, lanes=lanes)
+        assert many.lanes == lanes and len(many.lane_graphs) == lanes
+        np.testing.assert_allclose(many.optimizer.flat_g.cpu().numpy(), one.optimizer.flat_g.cpu().numpy(), rtol=1e-4, atol=1e-4)
+        l1 = [float(one(x, y)) for _ in range(2)]
+        l2 = [float(many(x, y)) for _ in range(2)]
     np.testing.assert_allclose(l2, l1, rtol=2e-4, atol=1e-6)
     assert_weights_close_after_adam(nets[1].state_dict(), nets[0].state_dict(), lr=5e-4, steps=4)
+    for k, net in enumerate(nets):      # the Adam step after the lanes' atomics: per tensor, at the gradient the lanes summed
+        audit.check(net, label='lanes=%d net %d' % (lanes, k))
+        assert [(r.step, r.lrs) for r in audit.records_of(net)] == [(i + 1, [5e-4]) for i in range(4)]
     # a batch the lanes cannot split evenly falls back to one graph
     assert training.GraphedTrainStep(nets[1], x[:3], y[:3], cw, ignore_idx=4, lanes=2).lanes == 1
 
@@ -438,11 +451,14 @@ def test_direct_gradient_sinks_equal_autograd_accumulation(hw, monkeypatch):
         m.load_state_dict(synth_state_dict(KEYS['espdnetue_s2.0_c5'], 4))
         m = m.to(DEV).eval()
         opt, losses, grads, weights = None, [], [], []
-        for _ in range(3):
-            l, opt = training.train_step(m, x, y, cw, opt, ignore_idx=4)
-            losses.append(float(l))
-            grads.append(opt.flat_g.clone())
-            weights.append(opt.flat_p.clone())
+        with StepAudit(m) as audit:
+            for _ in range(3):
+                l, opt = training.train_step(m, x, y, cw, opt, ignore_idx=4)
+                losses.append(float(l))
+                grads.append(opt.flat_g.clone())
+                weights.append(opt.flat_p.clone())
+        audit.check(m, label='grad sinks=%s %dx%d' % ((flag,) + hw))
+        assert audit.steps == [(i + 1, [5e-4]) for i in range(3)]
         outs.append((losses, grads, weights))
     np.testing.assert_allclose(outs[0][0], outs[1][0], rtol=1e-5)
     # Step 2 is the first one through the sinks and starts from weights that differ by float atomics' order only: tight.

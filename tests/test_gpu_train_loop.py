@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests.conftest import GOLDEN
+from tests.optim_shadow import StepAudit
 from tests.synth import assert_weights_close_after_adam, grad_sample_index, synth_state_dict
 from tests.train_loop_cases import (CLASS_WEIGHTS, IGNORE_IDX, LR, TOT_ITER, TRAIN_LOOP_CASES, WEIGHT_DECAY, WRITER_IDX0, loop_args,
                                     loop_batches)
@@ -55,6 +56,7 @@ def _run(name, epochs=None, restated=False):
     case = TRAIN_LOOP_CASES[name]
     spy = {'inside': False, 'inside_calls': [], 'graph_built': 0, 'graph_calls': 0, 'eager_steps': 0, 'reads': [], 'visual': []}
     mp = pytest.MonkeyPatch()
+    audit = StepAudit()          # every FlatAdam step of the run: device clones only while the spies count, host work after the loop
     try:
         def counted(owner, attr):
             orig = getattr(owner, attr)
@@ -73,10 +75,12 @@ def _run(name, epochs=None, restated=False):
         def init(self, *a, **k):
             spy['graph_built'] += 1
             spy['building'] = True
+            audit.tag = 'capture'          # the two steps the constructor takes on the batch that only shapes the capture
             try:
                 g_init(self, *a, **k)
             finally:
                 spy['building'] = False
+                audit.tag = None
 
         def call(self, *a, **k):
             spy['graph_calls'] += 1
@@ -112,20 +116,42 @@ def _run(name, epochs=None, restated=False):
         args, writer, idx = loop_args(case), Writer(), WRITER_IDX0
         out = {'returned': [], 'params': [], 'optimizers': []}
         epoch = 0
-        for n_epochs in case['phases']:
-            opt = torch.optim.Adam(m.parameters(), lr=LR, weight_decay=WEIGHT_DECAY)
-            out['optimizers'].append(opt)
-            for _ in range(n_epochs):
-                if epochs is not None and epoch >= epochs:
-                    break
-                idx = ns['train'](loader, m, crit, DEV, None, opt, TOT_ITER, 0, epoch, args, None, None, None, idx, None, writer, None)
-                out['returned'].append(int(idx))
-                out['params'].append(_sample(m))
-                epoch += 1
-        out.update(records=writer.records, spy=spy, epochs=epoch)
+        with audit:
+            audit.watch(m)
+            for n_epochs in case['phases']:
+                opt = torch.optim.Adam(m.parameters(), lr=LR, weight_decay=WEIGHT_DECAY)
+                out['optimizers'].append(opt)
+                for _ in range(n_epochs):
+                    if epochs is not None and epoch >= epochs:
+                        break
+                    idx = ns['train'](loader, m, crit, DEV, None, opt, TOT_ITER, 0, epoch, args, None, None, None, idx, None, writer, None)
+                    out['returned'].append(int(idx))
+                    out['params'].append(_sample(m))
+                    epoch += 1
+        out.update(records=writer.records, spy=spy, epochs=epoch, audit=_audit_summary(audit, m, name))
         return out
     finally:
         mp.undo()
+
+
+def _audit_summary(audit, model, label):
+    """Host side of the audit, after the loop: every recorded Adam step of every epoch and phase checked per tensor against float64
+    (frozen BatchNorm buffers and the 230 gradient-less tensors bit-identical), then what the tests assert about the sequence --
+    the device clones are dropped, the cached run keeps numbers only."""
+    if not audit.records:
+        return {'steps': [], 'fresh_moments_zero': [], 'first_step_from_entry_weights': None}
+    audit.check(model, label='train loop ' + label)
+    loop = [r for r in audit.records if r.tag is None]
+    entry = audit._entry[id(model)]
+    names = dict((id(p), n) for n, p in model.named_parameters())
+    opt = loop[0].opt
+    same = all(torch.equal(loop[0].pre[0][o:o + p.numel()].view(torch.int32), entry[names[id(p)]].reshape(-1).view(torch.int32))
+               for o, p in zip(opt.bucket.offsets, opt.params))
+    out = {'steps': [(r.tag, r.step, r.lrs[0]) for r in audit.records],
+           'fresh_moments_zero': [not bool(r.pre[2].any()) and not bool(r.pre[3].any()) for r in audit.records if r.step == 1],
+           'first_step_from_entry_weights': same, 'worst': dict(audit.worst)}
+    audit.records = []
+    return out
 
 
 _RUNS = {}
@@ -162,7 +188,11 @@ def test_train_loop_against_the_reference_loop(name, golden):
     Loss average: within the one-step bound of test_train_step_vs_reference_golden (rtol 2e-5, atol 1e-5).  Areas: per epoch and
     histogram an L1 distance of at most 2 * (the pixels whose top-2 margin of the reference's main head is below 1e-3), a number the
     fixture caps at 2 % of the pixels.  Parameters: assert_weights_close_after_adam over the steps applied so far -- a doubled first
-    step, moments kept across a fresh optimizer or a lost partial batch move far more than one per cent of the elements."""
+    step or a lost partial batch moves far more than one per cent of the elements.  Moments or a step count kept across a fresh
+    optimizer do NOT (Adam's next step is +-lr either way): those are caught by the step audit installed in `_run`
+    (tests/optim_shadow.py), which checks every Adam step of the loop per tensor against float64 at the step's own inputs and
+    whose recorded sequence is asserted below -- counts restarting at 1 on zero moments with each fresh optimizer, the poly
+    learning rate of every iteration, and a first step that starts from the entry weights (the capture batch leaves no trace)."""
     case, g, meta, got = TRAIN_LOOP_CASES[name], golden('train_loop'), META[name], _cached(name)
     steps, epochs = len(case['batches']), sum(case['phases'])
     ref = meta['records']
@@ -185,6 +215,18 @@ def test_train_loop_against_the_reference_loop(name, golden):
         assert_weights_close_after_adam(got['params'][e - 1], g[name + '.params_%d' % p], LR, done)
     assert got['spy']['visual'] == [['class_encoding', 'data', 'device', 'epoch', 'images', 'labels', 'writer']] * epochs
     assert len(got['spy']['reads']) == epochs
+    audited = got['audit']
+    if case['use_uncertainty']:          # the graphed path: FlatAdam steps (the restated body steps the caller's torch.optim.Adam)
+        from mspl_amd.training import lr_poly
+        lrs = [lr_poly(LR, i, TOT_ITER, case['power']) for i in range(steps)]
+        want = [('capture', 1, lrs[0]), ('capture', 2, lrs[0])]
+        for n_epochs in case['phases']:
+            want += [(None, e_ * steps + i + 1, lrs[i]) for e_ in range(n_epochs) for i in range(steps)]
+        assert audited['steps'] == want
+        assert audited['fresh_moments_zero'] == [True] * (1 + len(case['phases']))
+        assert audited['first_step_from_entry_weights'] is True
+    else:
+        assert audited['steps'] == []
 
 
 @pytest.mark.parametrize('name', ['loop_32x48', 'loop_64x96_tail'])

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 from oracle import train as otrain
 from tests.cases import LR_CASES, SUPERVISED_CASE
 from tests.conftest import GOLDEN
+from tests.optim_shadow import StepAudit
 from tests.synth import synth_input, synth_labels, synth_state_dict
 
 KEYS = json.load(open(os.path.join(GOLDEN, 'state_dict_keys.json')))
@@ -197,20 +198,24 @@ def test_supervised_step_vs_reference_golden(golden):
         else:
             got = float(params[n].grad.double().norm())
             assert abs(got - gn) <= 1e-2 * gn + 1e-5, (n, got, gn)
-    opt = supervised.FlatSGD(supervised.segmentation_param_groups(m, c['lr'], c['lr_mult']), lr=c['lr'] * c['lr_mult'],
-                             momentum=c['momentum'], weight_decay=c['weight_decay'])
-    before = {n: p.detach().clone() for n, p in params.items()}
-    opt.step()
-    torch.cuda.synchronize()
-    for n, moved in zip(names, g['moved']):
-        assert bool((params[n].detach() != before[n]).any()) == bool(moved), n
-    for i, k in enumerate(str(s) for s in g['keep']):
-        torch.testing.assert_close(params[k].detach().cpu(), torch.from_numpy(g['after_%d' % i]), rtol=1e-3, atol=2e-5)
-    sd = m.state_dict()
-    for i, k in enumerate(str(s) for s in g['stats']):
-        torch.testing.assert_close(sd[k].cpu(), torch.from_numpy(g['stat_%d' % i]), rtol=1e-4, atol=1e-5)
-    # the helper: a second iteration runs, the loss moves, every BatchNorm has seen two batches
-    loss2, out2, opt = supervised.train_seg_ue_step(m, x, labels, crit, opt)
+    with StepAudit(m) as audit:
+        opt = supervised.FlatSGD(supervised.segmentation_param_groups(m, c['lr'], c['lr_mult']), lr=c['lr'] * c['lr_mult'],
+                                 momentum=c['momentum'], weight_decay=c['weight_decay'])
+        before = {n: p.detach().clone() for n, p in params.items()}
+        opt.step()
+        torch.cuda.synchronize()
+        for n, moved in zip(names, g['moved']):
+            assert bool((params[n].detach() != before[n]).any()) == bool(moved), n
+        for i, k in enumerate(str(s) for s in g['keep']):
+            torch.testing.assert_close(params[k].detach().cpu(), torch.from_numpy(g['after_%d' % i]), rtol=1e-3, atol=2e-5)
+        sd = m.state_dict()
+        for i, k in enumerate(str(s) for s in g['stats']):
+            torch.testing.assert_close(sd[k].cpu(), torch.from_numpy(g['stat_%d' % i]), rtol=1e-4, atol=1e-5)
+        # the helper: a second iteration runs, the loss moves, every BatchNorm has seen two batches
+        loss2, out2, opt = supervised.train_seg_ue_step(m, x, labels, crit, opt)
+    # both SGD iterations, every element of every tensor and momentum buffer, per group (train() mode: the statistics move)
+    audit.check(m, frozen_buffers=False, label='supervised golden step')
+    assert audit.steps == [(1, [c['lr'], c['lr'] * c['lr_mult']]), (2, [c['lr'], c['lr'] * c['lr_mult']])]
     assert torch.isfinite(loss2) and out2.shape == logits.shape and float(loss2) != float(loss.detach())
     assert int(sd['base_net.level1.bn.num_batches_tracked']) == 2
     # inference afterwards uses the UPDATED running statistics (caches keyed on the buffers' versions)
@@ -235,12 +240,16 @@ def test_graphed_supervised_step_equals_eager():
         m.load_state_dict(synth_state_dict(KEYS['espdnetue_s%s_c%d' % (c['s'], c['classes'])], 5))
         nets.append(m.cuda().train())
     opt, eager = None, []
-    for _ in range(4):
-        l, _, opt = supervised.train_seg_ue_step(nets[0], x, y, crit, opt)
-        eager.append(float(l))
-    gs = supervised.GraphedSupervisedStep(nets[1], x, y, crit)                   # eager step 1 + captured step 2
-    graphed = [float(gs(x, y)[0]) for _ in range(2)]
+    with StepAudit(*nets) as audit:
+        for _ in range(4):
+            l, _, opt = supervised.train_seg_ue_step(nets[0], x, y, crit, opt)
+            eager.append(float(l))
+        gs = supervised.GraphedSupervisedStep(nets[1], x, y, crit)                   # eager step 1 + captured step 2
+        graphed = [float(gs(x, y)[0]) for _ in range(2)]
     np.testing.assert_allclose(graphed, eager[2:], rtol=5e-4, atol=1e-6)
+    for k, net in enumerate(nets):      # each run's own four SGD iterations per tensor, at that iteration's own gradient
+        audit.check(net, frozen_buffers=False, label='graphed supervised net %d' % k)
+        assert [r.step for r in audit.records_of(net)] == [1, 2, 3, 4]
     for (k, p), (_, q) in zip(nets[0].state_dict().items(), nets[1].state_dict().items()):
         # two runs of the same kernels: the float atomics of the weight-gradient / channel sums land in a different order, and the
         # coarsest BatchNorms normalise over a handful of values per channel (16 and 4 at 64 x 96), which amplifies that over the four
