@@ -510,6 +510,23 @@ int mspl_eval_epilogue_fwd(const float* main, const float* aux, const int64_t* t
                            unsigned long long* areas, uint8_t* labels, void* stream);
 int mspl_eval_batch_finalize(double* loss_sums, double* acc, int32_t batch_images, void* stream);
 
+/* The loss and meters of one train_seg_ue iteration from ONE read of the full-size `outputs + 0.5 * out_aux` logits
+ * (utilities/train_eval_seg.py:202 `criterion(outputs, target).mean()`, :216 `miou_class.get_iou(outputs, target)` with its two
+ * device-to-host copies): pred (N,C,HW) fp32, target (N,HW) int64, class_weights NULL = 1.
+ *     sums[0] += sum_valid w[t] * (lse(pred) - pred[t]),  sums[1] += sum_valid w[t]      (valid: 0 <= t < C and t != ignore_index,
+ *         the rule of mspl_weighted_ce_fwd; doubles)
+ *     areas[0..3K) += [area_inter | area_pred | area_mask] of MIOU(K).get_iou(pred, target) in the uint8 arithmetic of
+ *         utilities/metrics/segmentation_miou.py:28-41 -- exactly what mspl_miou_areas_fwd gives on the same logits; K =
+ *         miou_classes (1..64, else MSPL_ERR_UNSUPPORTED); areas may be NULL (the loss alone).
+ * Both are ACCUMULATED into (caller zeroes).
+ * mspl_ce_flood_finalize: `loss = (loss - b).abs() + b; losses.update(loss.item(), inputs.size(0))` (:221-222) on the device, in
+ * fp32 and the reference's order: l = float(sums[0]) / float(sums[1]); out3[0] = |l - b| + b; out3[1] = sign(l - b) (0 at
+ * equality, the factor of torch's abs backward); out3[2] = float(sums[1]) (the `den` of mspl_weighted_ce_bwd);
+ * meter[0] += double(out3[0]) * batch_images (meter may be NULL); sums is cleared for the next step. */
+int mspl_ce_meters_fwd(const float* pred, const int64_t* target, const float* class_weights, int32_t ignore_index, int32_t N,
+                       int32_t C, int32_t HW, int32_t miou_classes, double* sums, unsigned long long* areas, void* stream);
+int mspl_ce_flood_finalize(double* sums, float flood_level, int32_t batch_images, float* out3, double* meter, void* stream);
+
 /* Stand-alone loss modules (callers that compose them themselves instead of the fused K11 form):
  *  PixelwiseKLD.forward (loss_fns/segmentation_loss.py:181-189): kld (N,HW) = sum_c softmax(d1)*(log_softmax(d1)-log_softmax(d2));
  *  its backward: gd1/gd2 (N,C,HW) from gkld (N,HW); either output may be NULL. */

@@ -1436,3 +1436,52 @@ def uw_loss_heads(main, aux, target, class_weights, ce_scale=20.0, out_scale=1.0
     `classes`, `areas` (int64[3 * classes]) and `meter` (float64[2]) on the device, e.g. training.TrainMeters: the same launch adds
     MIOU(classes)'s three area histograms of the up-sampled main head and loss * batch size into them."""
     return UWLossHeadsFn.apply(main, aux, target, class_weights, ce_scale, out_scale, root, meters)
+
+
+class FloodedCEMetersFn(torch.autograd.Function):
+    """`loss = criterion(outputs, target).mean(); miou_class.get_iou(outputs, target); loss = (loss - b).abs() + b;
+    losses.update(loss.item(), n)` of train_seg_ue (utilities/train_eval_seg.py:202-222) for SegmentationLoss('ce') as one node of two
+    launches: mspl_ce_meters_fwd reads the logits once for the cross-entropy sums and the three area histograms,
+    mspl_ce_flood_finalize floods the loss and adds loss * n to the epoch's meter.  Backward is mspl_weighted_ce_bwd with the
+    upstream gradient times sign(loss - b), the factor torch's abs backward applies."""
+
+    @staticmethod
+    def forward(ctx, outputs, target, cw, ignore_idx, b, meters):
+        outputs = _c(outputs)
+        N, C = outputs.shape[:2]
+        hw = outputs[0, 0].numel()
+        target = _c(target.to(torch.int64))
+        if not target.is_cuda or target.numel() != N * hw:
+            raise RuntimeError('mspl_amd: target must be a CUDA tensor of %d labels, got %s' % (N * hw, tuple(target.shape)))
+        cw = None if cw is None else _c(cw.float())
+        out3 = torch.empty(3, device=outputs.device, dtype=torch.float32)
+        if meters is None:
+            sums = torch.zeros(2, device=outputs.device, dtype=torch.float64)
+            check(lib.mspl_ce_meters_fwd(_p(outputs), _p(target), _p(cw), int(ignore_idx), N, C, hw, 1, _p(sums), None, _stream()))
+            check(lib.mspl_ce_flood_finalize(_p(sums), float(b), N, _p(out3), None, _stream()))
+        else:
+            # (meters.sums is zero on entry: the finalize launch of the step before cleared it)
+            check(lib.mspl_ce_meters_fwd(_p(outputs), _p(target), _p(cw), int(ignore_idx), N, C, hw, int(meters.classes),
+                                         _p(meters.sums), _p(meters.areas), _stream()))
+            check(lib.mspl_ce_flood_finalize(_p(meters.sums), float(b), N, _p(out3), _p(meters.meter), _stream()))
+        ctx.save_for_backward(outputs, target, cw, out3)
+        ctx.ignore = int(ignore_idx)
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        outputs, target, cw, out3 = ctx.saved_tensors
+        N, C = outputs.shape[:2]
+        hw = outputs[0, 0].numel()
+        g = _c((grad_out.to(torch.float32) * out3[1]).reshape(1))
+        gp = torch.empty_like(outputs)
+        check(lib.mspl_weighted_ce_bwd(_p(outputs), _p(target), None, _p(cw), ctx.ignore, N, C, hw, _p(g), _p(out3[2:]), _p(gp), None,
+                                       _stream()))
+        return gp, None, None, None, None, None
+
+
+def flooded_ce_meters(outputs, target, cw, ignore_idx, b, meters=None):
+    """flood(CrossEntropyLoss(cw, ignore_idx)(outputs, target), b) of (N,C,H,W) logits.  meters: an object with `classes`, `areas`
+    (int64[3 * classes]), `meter` (float64[2]) and `sums` (float64[2], zero between steps) on the device, e.g.
+    supervised.SupervisedMeters: the same launches add MIOU(classes)'s area histograms of `outputs` and loss * batch size."""
+    return FloodedCEMetersFn.apply(outputs, target, cw, ignore_idx, b, meters)

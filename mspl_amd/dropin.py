@@ -94,7 +94,10 @@ def install_dropin(force=False, script=None, train_loops=False):
     script: the globals() (or module object) of uest_seg_multi_os.py -- the functions the script defines itself (get_output,
     merge_outputs, update_image_list, generate_pseudo_label, generate_pseudo_label_multi_model) are rebound there too
     (mspl_amd.script.patch_script; call after the script's own definitions).  train_loops=True also rebinds the script's `train`
-    to the loop on the graphed training step (mspl_amd.script.train)."""
+    to the loop on the graphed training step (mspl_amd.script.train) and, independently of `script`, puts `train_seg_ue`
+    (mspl_amd.script.train_seg_ue, the supervised loop on the graphed supervised step that train_segmentation.py:368 binds) into the
+    `utilities.train_eval_seg` alias beside `val_seg_ue`; the default leaves `train_seg_ue` to the overlay (the reference's own
+    function)."""
     from . import layers as L, models as M, uest as U
     names = ['nn_layers', 'model', 'loss_fns']
     if not force:
@@ -131,7 +134,11 @@ def install_dropin(force=False, script=None, train_loops=False):
     from . import metrics as Q
     _alias('utilities.metrics.segmentation_miou', MIOU=Q.MIOU)
     from . import evaluation as E
-    _alias('utilities.train_eval_seg', val_seg_ue=E.val_seg_ue)
+    if train_loops:
+        from .script import train_seg_ue
+        _alias('utilities.train_eval_seg', val_seg_ue=E.val_seg_ue, train_seg_ue=train_seg_ue)
+    else:
+        _alias('utilities.train_eval_seg', val_seg_ue=E.val_seg_ue)
     _alias('loss_fns.segmentation_loss', PixelwiseKLD=S.PixelwiseKLD,
            UncertaintyWeightedSegmentationLoss=S.UncertaintyWeightedSegmentationLoss,
            SegmentationLoss=S.SegmentationLoss, NIDLoss=S.NIDLoss)

@@ -246,3 +246,132 @@ def patch_script(namespace, train=False):
         ns['train'] = _bound_train(ns)
         return sorted(list(SCRIPT_FUNCTIONS) + ['train'])
     return sorted(SCRIPT_FUNCTIONS)
+
+
+# ------------------------------------------------------------- train_seg_ue() (utilities/train_eval_seg.py:164-247, train_segmentation.py:368)
+def _supervised_fast_path(model, criterion, optimizer, add_criterion, device, use_depth=False):
+    """The settings of the shipped train_segmentation.py runs that supervised.GraphedSupervisedStep computes: the drop-in two-head
+    ESPDNet-UE, the drop-in SegmentationLoss('ce'), no additional criterion, plain momentum SGD over the script's 2 or 3 learning-rate
+    groups, a CUDA device.  RGB-D batches (use_depth) take the restated body."""
+    from . import losses, models
+    if _FORCE_RESTATED or add_criterion is not None or use_depth:
+        return False
+    if type(model) is not models.ESPDNetwithUncertaintyEstimation or getattr(model, 'aux_layer', -1) < 0:
+        return False
+    if type(criterion) is not losses.SegmentationLoss or criterion.loss_type != 'ce':
+        return False
+    if type(optimizer) is not torch.optim.SGD or len(optimizer.param_groups) not in (2, 3):
+        return False
+    for g in optimizer.param_groups:
+        if g.get('dampening', 0) != 0 or g.get('nesterov', False) or g.get('maximize', False):
+            return False
+    try:
+        return torch.device(device).type == 'cuda'
+    except (RuntimeError, TypeError):
+        return False
+
+
+def _train_seg_ue_fast(model, dataset_loader, optimizer, criterion, device, meters, state):
+    """The step loop on supervised.GraphedSupervisedStep: no .item(), no .cpu(), no synchronize inside.  The caller's SGD never steps
+    (its state stays empty); its groups' hyper-parameters are read into the FlatSGD of the graphed step at every iteration (the
+    script writes the learning rates per epoch, train_segmentation.py:353-362).  One graphed step per model is kept on the model
+    object and reused across epochs; a new optimizer object starts with zero momentum, as a fresh torch.optim.SGD would."""
+    import weakref
+    from . import supervised
+    if state.get('step') is not None:
+        # (an epoch on the restated body in between leaves the caller's own gradient tensors on the parameters)
+        state['step'].optimizer.reattach()
+    for batch in dataset_loader:
+        inputs = batch[0].to(device=device)
+        target = batch[1].to(device=device)
+        gs = state.get('step')
+        if gs is None:
+            # the first batch shapes the capture and is NOT applied by it (consume_first_batch=False)
+            gs = supervised.GraphedSupervisedStep(model, inputs, target, criterion, meters=meters, consume_first_batch=False,
+                                                  param_groups=optimizer.param_groups)
+            state['step'] = gs
+            state['optimizer'] = None
+        if gs.meters is not meters:
+            raise RuntimeError('mspl_amd.script.train_seg_ue: the graphed step of this model was captured with other meters')
+        gs.set_criterion(criterion)
+        if state.get('optimizer') is None or state['optimizer']() is not optimizer:
+            if not gs.optimizer.same_partition(optimizer.param_groups):
+                raise RuntimeError('mspl_amd.script.train_seg_ue: this optimizer splits the parameters into other groups than the one the '
+                                   "graphed step of this model was built from; call script.release_supervised_loop(model) first")
+            gs.optimizer.reset(optimizer.param_groups)
+            state['optimizer'] = weakref.ref(optimizer)
+        for g, src in zip(gs.optimizer.param_groups, optimizer.param_groups):
+            g['lr'], g['momentum'], g['weight_decay'] = src['lr'], src['momentum'], src['weight_decay']
+        if tuple(inputs.shape) == tuple(gs.inputs.shape):
+            gs(inputs, target)
+        else:                                                    # the loader has no drop_last: same FlatSGD, same meters, eager
+            supervised.train_seg_ue_step(model, inputs, target, criterion, gs.optimizer, b=gs.b, meters=meters)
+
+
+def _train_seg_ue_restated(model, dataset_loader, optimizer, criterion, device, use_depth, add_criterion, weight, meters):
+    """The reference body (:179-228) on the drop-in modules with the caller's own optimizer; the meters stay on the device.  (The
+    reference also evaluates PixelwiseKLD at :196 and never uses the result; that launch is left out.)"""
+    from collections import OrderedDict
+    from . import layers, supervised
+    for batch in dataset_loader:
+        inputs = batch[0].to(device=device)
+        target = batch[1].to(device=device)
+        outputs = model(inputs, batch[2].to(device=device)) if use_depth else model(inputs)
+        if isinstance(outputs, OrderedDict):
+            out_aux, outputs = outputs['aux'], outputs['out']
+        else:
+            out_aux, outputs = outputs[1], outputs[0]
+        outputs = outputs + 0.5 * out_aux
+        loss = criterion(outputs, target).mean()
+        loss2 = None
+        if add_criterion is not None:
+            loss2 = add_criterion(inputs, outputs.to(device)) * weight
+            loss = loss + loss2
+        loss = supervised.flood(loss)
+        meters.add(outputs, target, loss, inputs.size(0), extra=loss2)
+        meters.count(inputs.size(0))
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        layers.bump_param_epoch()       # (torch.optim bumps the version counters the caches watch; this covers an optimizer that does not)
+
+
+def release_supervised_loop(model):
+    """Drop what train_seg_ue keeps on the model object between epochs (`model.__dict__['_mspl_supervised_loop']`: the graphed step
+    with its static batch, graph and FlatSGD, and the meters, bound to the first call's device and num_classes).  The parameters
+    stay where they are (views of the flat buffer, which lives as long as they do)."""
+    model.__dict__.pop('_mspl_supervised_loop', None)
+
+
+def train_seg_ue(model, dataset_loader, optimizer, criterion, num_classes, epoch, device='cuda', use_depth=False, add_criterion=None,
+                 weight=1.0, greenhouse_use_trav=False):
+    """utilities/train_eval_seg.py:164-247 with its own signature; returns (iou float32[num_classes - 1], average flooded loss), where
+    iou = inter / (union + 1e-10) over the epoch's summed areas of the `out + 0.5 * aux` logits (`greenhouse_use_trav` only selects
+    a mean the reference computes and drops, :241-245).  With the shipped settings (`_supervised_fast_path`) the iterations run on
+    supervised.GraphedSupervisedStep with loss and meters taken in one read of the logits; the caller's SGD then never steps and holds
+    no state.  Everything else -- an additional criterion with `weight`, RGB-D batches, other models, losses or optimizers -- runs the
+    reference body on the drop-in modules with the caller's optimizer.  Nothing inside the loop synchronises, so the reference's
+    running log line of every tenth iteration is not printed; one line follows the epoch.  Meters are per rank.  The graphed step
+    and the meters are kept on the model object until release_supervised_loop(model); an epoch on the restated body may come in between
+    (the flat gradient views are re-attached at the next graphed epoch), an optimizer with another split of the parameters raises."""
+    from . import supervised
+    model.train()
+    state = model.__dict__.setdefault('_mspl_supervised_loop', {})
+    meters = state.get('meters')
+    if meters is None:
+        meters = state['meters'] = supervised.SupervisedMeters(num_classes - 1, device)       # MIOU(num_classes - 1), :175
+    elif meters.classes != num_classes - 1 or meters.areas.device.type != torch.device(device).type:
+        raise RuntimeError('mspl_amd.script.train_seg_ue: this model was run with num_classes=%d on %s before; call '
+                           'script.release_supervised_loop(model) first' % (meters.classes + 1, meters.areas.device))
+    meters.reset()
+    print("train_seg_ue()")
+    if _supervised_fast_path(model, criterion, optimizer, add_criterion, device, use_depth):
+        _train_seg_ue_fast(model, dataset_loader, optimizer, criterion, device, meters, state)
+    else:
+        _train_seg_ue_restated(model, dataset_loader, optimizer, criterion, device, use_depth, add_criterion, weight, meters)
+    r = meters.read()                   # the epoch's one device-to-host copy
+    import numpy as np
+    iou = (r['inter'] / (r['union'] + 1e-10)).astype(np.float32)            # :240
+    nid_avg = r['extra_sum'] / r['steps'] if (add_criterion is not None and r['steps']) else 0.0
+    print("Epoch: %d[%d steps]\t\tLoss:%.4f\t\tmiou:%.4f\t\tNID loss:%.4f" % (epoch, r['steps'], r['loss_avg'], iou.mean() * 100, nid_avg))
+    return iou, r['loss_avg']

@@ -23,6 +23,7 @@ from . import dist as mdist
 from . import layers
 from ._native import check, lib
 from .ops import _p, _stream
+from .training import TrainMeters
 
 FLOOD_LEVEL = 0.015          # utilities/train_eval_seg.py:178
 
@@ -58,8 +59,45 @@ class FlatSGD:
         self.params = flat
         self.step_count = 0
 
+    def reset(self, groups=None):
+        """Start over as a fresh torch.optim.SGD would (train_segmentation.py builds one per run): zero momentum buffer and the
+        first-step rule (buf = gradient) again.  groups: torch-style parameter groups in this optimizer's group order whose `lr`,
+        `momentum` and `weight_decay` are taken over."""
+        if groups is not None:
+            groups = list(groups)
+            if len(groups) != len(self.param_groups):
+                raise ValueError('FlatSGD.reset: %d groups given, the optimizer has %d' % (len(groups), len(self.param_groups)))
+            for g, src in zip(self.param_groups, groups):
+                for k in ('lr', 'momentum', 'weight_decay'):
+                    if k in src:
+                        g[k] = src[k]
+        self.buf.zero_()
+        self.step_count = 0
+
     def zero_grad(self):
         self.flat_g.zero_()
+
+    def same_partition(self, groups):
+        """True when torch-style `groups` split this optimizer's parameters the way it was built: as many groups, and every
+        parameter of group i listed in groups[i]."""
+        groups = list(groups)
+        if len(groups) != len(self.param_groups):
+            return False
+        return all(set(id(p) for p in mine['params']) <= set(id(p) for p in theirs['params'])
+                   for mine, theirs in zip(self.param_groups, groups))
+
+    def reattach(self):
+        """Make every parameter's .grad the view of the flat gradient buffer again (another optimizer's zero_grad() sets it to None
+        and autograd then allocates a tensor of its own, which this optimizer would never read).  Raises when a parameter's storage
+        no longer is its view of the flat parameter buffer (a model moved or re-created since)."""
+        b = self.bucket
+        for p, off in zip(b.params, b.offsets):
+            if p.data_ptr() != b.flat_p.data_ptr() + 4 * off:
+                raise RuntimeError('FlatSGD: a parameter no longer lives in the flat parameter buffer (the model was moved or its '
+                                   'tensors replaced); build a new step')
+            g = p.grad
+            if g is None or g.data_ptr() != b.flat.data_ptr() + 4 * off:
+                p.grad = b.flat[off:off + p.numel()].view_as(p)
 
     def all_reduce_grads(self):
         self.bucket.all_reduce()
@@ -116,29 +154,83 @@ def two_head_outputs(model, inputs, depth=None):
     return out[0] + 0.5 * out[1]
 
 
+class SupervisedMeters(TrainMeters):
+    """The per-epoch meters of train_seg_ue (utilities/train_eval_seg.py:166-175, 216-222, 240) on the device: training.TrainMeters
+    as it stands (`areas` int64[3 K], `meter` float64[2] = [sum of flooded loss * batch size, sum of the additional loss], host step
+    and image counts, `add()` for the paths the fused node does not cover, `read()` as the one sync of an epoch) plus `sums`, the
+    float64[2] cross-entropy sums of the step in flight that autograd.flooded_ce_meters accumulates and clears.
+
+    What MIOU is taken on differs from train(): here the SUMMED `main + 0.5 * aux` logits with K = num_classes - 1 (:175, :216),
+    there the main head alone.  Meters are per rank: a multi-GPU run all-reduces gradients, not these sums."""
+
+    def __init__(self, classes, device='cuda'):
+        super().__init__(classes, device)
+        self.sums = torch.zeros(2, dtype=torch.float64, device=device)
+
+    def reset(self):
+        super().reset()
+        self.sums.zero_()
+
+
+def _fused_loss(criterion, add_criterion, meters):
+    """The settings autograd.flooded_ce_meters computes: the drop-in SegmentationLoss('ce') alone, with meters to fill."""
+    from . import losses
+    return meters is not None and add_criterion is None and type(criterion) is losses.SegmentationLoss
+
+
+def _sgd_groups(param_groups):
+    """A caller's torch.optim.SGD groups as FlatSGD groups: same parameters, same group order."""
+    return [{'params': list(g['params']), 'lr': g['lr'], 'momentum': g.get('momentum', 0.0),
+             'weight_decay': g.get('weight_decay', 0.0)} for g in param_groups]
+
+
 def train_seg_ue_step(model, inputs, target, criterion, optimizer=None, depth=None, add_criterion=None, weight=1.0,
-                      lr=0.009, lr_mult=10.0, momentum=0.9, weight_decay=4e-5, b=FLOOD_LEVEL):
+                      lr=0.009, lr_mult=10.0, momentum=0.9, weight_decay=4e-5, b=FLOOD_LEVEL, *, meters=None, param_groups=None):
     """One iteration of train_seg_ue (utilities/train_eval_seg.py:179-225) for a two-head model in train() mode.
     Returns (flooded loss, (main + 0.5*aux) logits detached -- what the reference hands to MIOU --, optimizer).  Pass
-    optimizer=None on the first call: it is built after the first backward from segmentation_param_groups."""
+    optimizer=None on the first call: it is built after the first backward from segmentation_param_groups, or from
+    `param_groups` (a caller's torch.optim.SGD groups: same parameters, same order) when given.  meters: a SupervisedMeters the
+    iteration is added to -- inside the loss launches for SegmentationLoss('ce') without add_criterion, by meters.add() otherwise."""
     if optimizer is not None:
         optimizer.zero_grad()
     tr = getattr(optimizer, 'transposer', None)
     with torch.enable_grad(), ag.grad_sinks(), (tr.active() if tr is not None else ag.collect_conv_weights()) as got:
         layers.prefold_frozen_bn(model)
         outputs = two_head_outputs(model, inputs, depth)
-        loss = criterion(outputs, target).mean()
-        if add_criterion is not None:
-            loss = loss + add_criterion(inputs, outputs) * weight
-        loss = flood(loss, b)
+        if meters is None:
+            loss = criterion(outputs, target).mean()
+            if add_criterion is not None:
+                loss = loss + add_criterion(inputs, outputs) * weight
+            loss = flood(loss, b)
+        else:
+            loss = _metered_loss(criterion, outputs, target, inputs, add_criterion, weight, b, meters)
         loss.backward()
+    if meters is not None:
+        meters.count(inputs.shape[0])
     if optimizer is None:
-        optimizer = FlatSGD(segmentation_param_groups(model, lr, lr_mult, depth is not None), lr=lr * lr_mult,
-                            momentum=momentum, weight_decay=weight_decay)
+        groups = _sgd_groups(param_groups) if param_groups is not None else segmentation_param_groups(model, lr, lr_mult, depth is not None)
+        optimizer = FlatSGD(groups, lr=lr * lr_mult, momentum=momentum, weight_decay=weight_decay)
         optimizer.transposer = ag.WeightTransposer(got)      # (after FlatSGD: the parameters now live in its flat buffer)
     optimizer.all_reduce_grads()
     optimizer.step()
     return loss.detach(), outputs.detach(), optimizer
+
+
+def _metered_loss(criterion, outputs, target, inputs, add_criterion, weight, b, meters, cw=None):
+    """Loss of the iteration with `meters` filled (the step count stays with the caller).  cw: the class-weight tensor the fused node
+    reads (a graph passes its own static copy)."""
+    if _fused_loss(criterion, add_criterion, meters):
+        if cw is None and criterion.class_wts is not None:
+            cw = criterion.class_wts.to(outputs.device)
+        return ag.flooded_ce_meters(outputs, target, cw, int(criterion.ignore_idx), b, meters)
+    loss = criterion(outputs, target).mean()
+    loss2 = None
+    if add_criterion is not None:
+        loss2 = add_criterion(inputs, outputs) * weight
+        loss = loss + loss2
+    loss = flood(loss, b)
+    meters.add(outputs, target, loss, inputs.shape[0], extra=loss2)
+    return loss
 
 
 class GraphedSupervisedStep:
@@ -148,13 +240,27 @@ class GraphedSupervisedStep:
     shapes are fixed at construction.  BatchNorm running statistics and num_batches_tracked advance inside the graph."""
 
     def __init__(self, model, inputs, target, criterion, depth=None, lr=0.009, lr_mult=10.0, momentum=0.9, weight_decay=4e-5,
-                 b=FLOOD_LEVEL):
+                 b=FLOOD_LEVEL, *, meters=None, consume_first_batch=True, param_groups=None):
+        """meters: a SupervisedMeters captured inside the graph (the loss then goes through autograd.flooded_ce_meters); it is reset
+        when the constructor returns.  param_groups: a caller's torch.optim.SGD groups to build FlatSGD from instead of
+        segmentation_param_groups.  consume_first_batch=False: the construction batch only shapes the capture -- the constructor
+        takes two SGD steps on it (the eager iteration, then the captured one), and a loop applies each batch exactly once, so
+        everything that moved is put back to its value on entry: the parameters, every buffer of the model (BatchNorm
+        running_mean, running_var and num_batches_tracked advance in train() mode), a zero momentum buffer and step count."""
         self.model, self.criterion, self.b = model, criterion, b
+        self.meters = meters
+        entry = None
+        if not consume_first_batch:
+            entry = ([p.detach().clone() for p in model.parameters()], dict((n, t.detach().clone()) for n, t in model.named_buffers()))
         self.inputs = inputs.detach().clone()
         self.target = target.detach().clone()
         self.depth = None if depth is None else depth.detach().clone()
         _, _, self.optimizer = train_seg_ue_step(model, self.inputs, self.target, criterion, None, self.depth, None, 1.0, lr, lr_mult,
-                                                 momentum, weight_decay, b)
+                                                 momentum, weight_decay, b, meters=meters, param_groups=param_groups)
+        # the class weights the captured loss node reads: a copy of this object's own, refreshed by set_criterion
+        self.cw = None
+        if _fused_loss(criterion, None, meters) and criterion.class_wts is not None:
+            self.cw = criterion.class_wts.detach().to(self.inputs.device, torch.float32).clone()
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
@@ -162,14 +268,42 @@ class GraphedSupervisedStep:
             with torch.enable_grad(), ag.grad_sinks(), self.optimizer.transposer.active():
                 layers.prefold_frozen_bn(model)
                 self.outputs = two_head_outputs(model, self.inputs, self.depth)
-                self.loss = flood(criterion(self.outputs, self.target).mean(), b)
+                if meters is None:
+                    self.loss = flood(criterion(self.outputs, self.target).mean(), b)
+                else:
+                    self.loss = _metered_loss(criterion, self.outputs, self.target, self.inputs, None, 1.0, b, meters, cw=self.cw)
                 self.loss.backward()
         self._finish()                                  # the capture did not execute: run the iteration it recorded
+        if entry is not None:
+            with torch.no_grad():
+                for p, p0 in zip(model.parameters(), entry[0]):       # (.data are views of the flat buffer by now: written in place)
+                    p.copy_(p0)
+                for n, t in model.named_buffers():
+                    t.copy_(entry[1][n])
+            self.optimizer.reset()
+            layers.bump_param_epoch()
+        if meters is not None:
+            meters.reset()
+
+    def set_criterion(self, criterion):
+        """Another criterion object of the same kind (a script that rebuilds it): its class weights are copied into the tensor the
+        graph reads; anything the capture cannot follow raises."""
+        if criterion is self.criterion:
+            return
+        if self.meters is None or not _fused_loss(criterion, None, self.meters) or not _fused_loss(self.criterion, None, self.meters):
+            raise RuntimeError('GraphedSupervisedStep: the step was captured with another criterion object')
+        if int(criterion.ignore_idx) != int(self.criterion.ignore_idx) or (criterion.class_wts is None) != (self.cw is None):
+            raise RuntimeError('GraphedSupervisedStep: the new criterion differs in ignore_idx or in having class weights')
+        if self.cw is not None:
+            self.cw.copy_(criterion.class_wts.to(self.cw.device, torch.float32))
+        self.criterion = criterion
 
     def _finish(self):
         self.graph.replay()
         self.optimizer.all_reduce_grads()
         self.optimizer.step()
+        if self.meters is not None:
+            self.meters.count(self.inputs.shape[0])
         return self.loss.detach(), self.outputs.detach()
 
     def __call__(self, inputs, target, depth=None):
