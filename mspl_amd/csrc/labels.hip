@@ -19,13 +19,15 @@ struct LeGeom {
     float shm, swm, sha, swa;
 };
 
-// One thread per output pixel, ONE pass over the classes with running (online) maxima, so nothing but a
-// handful of scalars lives in registers whatever C is:
+// One thread per output pixel; nothing but a handful of scalars lives in registers whatever C is.  First pass over the classes:
 //   argmax_c o_c                      (strict '>' keeps the first maximum, like np.argmax)
-//   lse(main), lse(aux)               (running max + rescaled sum)
-//   E_p1[main - aux]                  (rescaled with lse(main)'s running max)
-//   KL(main || aux) = E_p1[main - aux] - lse(main) + lse(aux)
-// Softmax probabilities, when requested, take a second pass (get_output's drop-in form only).
+//   M1 = max main, M2 = max aux
+// The KL map, when requested, takes a second pass that interpolates again (this form is not on the hot path):
+//   S1 = sum exp(main - M1), S2 = sum exp(aux - M2), T1 = sum exp(main - M1) * ((main - M1) - (aux - M2))
+//   KL(main || aux) = T1 / S1 - log S1 + log S2
+// Every term is centred on its head's maximum, so none has the size of the logits: T1 / S1 - lse(main) + lse(aux) on the raw
+// logits cancels three such terms and errs by half an ulp of the largest logit, negative KL included.
+// Softmax probabilities, when requested, take a further pass (get_output's drop-in form only).
 __global__ __launch_bounds__(256) void label_epilogue_kernel(const float* __restrict__ mainp,
                                                              const float* __restrict__ auxp, LeGeom g,
                                                              const uint8_t* __restrict__ lut,
@@ -72,8 +74,7 @@ __global__ __launch_bounds__(256) void label_epilogue_kernel(const float* __rest
     };
 
     float omax = -INFINITY;  int best = 0;
-    float M1 = -INFINITY, S1 = 0.f, T1 = 0.f;   // lse(main) state and sum exp(m - M1) * (m - a)
-    float M2 = -INFINITY, S2 = 0.f;             // lse(aux) state
+    float M1 = -INFINITY, M2 = -INFINITY;       // maxima of the two heads, known before the sums
 #pragma unroll 2
     for (int c = 0; c < g.C; ++c) {
         const float m = interp_main(c);
@@ -82,17 +83,25 @@ __global__ __launch_bounds__(256) void label_epilogue_kernel(const float* __rest
         if (o > omax) { omax = o; best = c; }
         if (main_up) main_up[((size_t)n * g.C + c) * hw + pix] = m;
         if (aux_up && ab) aux_up[((size_t)n * g.C + c) * hw + pix] = a;
-        if (kld && ab) {
-            if (m > M1) { const float f = expf(M1 - m); S1 *= f; T1 *= f; M1 = m; }
-            const float e1 = expf(m - M1);
-            S1 += e1;
-            T1 = fmaf(e1, m - a, T1);
-            if (a > M2) { S2 *= expf(M2 - a); M2 = a; }
-            S2 += expf(a - M2);
-        }
+        M1 = fmaxf(M1, m);
+        M2 = fmaxf(M2, a);
     }
     if (labels) labels[(size_t)n * hw + pix] = lut ? lut[best] : (uint8_t)best;
-    if (kld) kld[(size_t)n * hw + pix] = ab ? (T1 / S1 - (M1 + logf(S1)) + (M2 + logf(S2))) : 0.f;
+    if (kld) {
+        float k = 0.f;
+        if (ab) {
+            float S1 = 0.f, T1 = 0.f, S2 = 0.f;     // sum exp(m - M1), sum exp(m - M1) * ((m - M1) - (a - M2)), sum exp(a - M2)
+            for (int c = 0; c < g.C; ++c) {
+                const float d1 = interp_main(c) - M1, d2 = interp_aux(c) - M2;
+                const float e1 = expf(d1);
+                S1 += e1;
+                T1 = fmaf(e1, d1 - d2, T1);
+                S2 += expf(d2);
+            }
+            k = T1 / S1 - logf(S1) + logf(S2);
+        }
+        kld[(size_t)n * hw + pix] = k;
+    }
     if (prob) {
         float s = 0.f;
         for (int c = 0; c < g.C; ++c) s += expf(interp_main(c) + 0.5f * (ab ? interp_aux(c) : 0.f) - omax);
@@ -172,13 +181,16 @@ __global__ __launch_bounds__(256) void label_epilogue_reg_kernel(const float* __
 #pragma unroll
             for (int c = 0; c < CMAX; ++c) {
                 if (c < g.C) {
-                    const float e1 = __expf(m[c] - M1);      // v_exp_f32 path: arguments are <= 0, relative error ~1e-7
+                    // centred: both differences are <= 0 and small wherever e1 is not, so nothing of the size of the logits
+                    // is left to cancel (T1 / S1 - lse(main) + lse(aux) on raw logits erred by half an ulp of the largest one)
+                    const float d1 = m[c] - M1, d2 = a[c] - M2;
+                    const float e1 = __expf(d1);             // v_exp_f32 path: arguments are <= 0, relative error ~1e-7
                     S1 += e1;
-                    T1 = fmaf(e1, m[c] - a[c], T1);
-                    S2 += __expf(a[c] - M2);
+                    T1 = fmaf(e1, d1 - d2, T1);
+                    S2 += __expf(d2);
                 }
             }
-            k = T1 / S1 - (M1 + __logf(S1)) + (M2 + __logf(S2));
+            k = T1 / S1 - __logf(S1) + __logf(S2);
         }
         kld[pix] = k;
     }
@@ -441,13 +453,14 @@ __global__ __launch_bounds__(256) void label_epilogue_lds_kernel(const float* __
 #pragma unroll
                         for (int c = 0; c < CMAX; ++c) {
                             if (EXACT || c < g.C) {
-                                const float e1 = __expf(m[c] - M1);
+                                const float d1 = m[c] - M1, d2 = a[c] - M2;     // centred, as in the register form
+                                const float e1 = __expf(d1);
                                 S1 += e1;
-                                T1 = fmaf(e1, m[c] - a[c], T1);
-                                S2 += __expf(a[c] - M2);
+                                T1 = fmaf(e1, d1 - d2, T1);
+                                S2 += __expf(d2);
                             }
                         }
-                        k = T1 / S1 - (M1 + __logf(S1)) + (M2 + __logf(S2));
+                        k = T1 / S1 - __logf(S1) + __logf(S2);
                     }
                     kld[pix] = k;
                 }

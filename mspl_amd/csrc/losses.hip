@@ -3,7 +3,8 @@
 //   UncertaintyWeightedSegmentationLoss.forward :155-175   mean_{n,p}( w[t] * -log_softmax(pred)[t] * exp(-u) )   (mean over ALL pixels)
 //   SegmentationLoss (loss_type 'ce')          :11-52     nn.CrossEntropyLoss(weight, ignore_index): sum(w[t]*nll) / sum_{valid}(w[t])
 // The fused K11 kernel (train.hip) covers the exact uest combination in one pass; these serve callers that compose
-// the modules themselves.  One thread per pixel, classes streamed with a running log-sum-exp; NCHW fp32, int64 targets.
+// the modules themselves.  One thread per pixel; the cross entropy streams the classes with a running log-sum-exp, the KL takes each
+// head's maximum first (lsm_norm); NCHW fp32, int64 targets.
 #include <algorithm>
 
 #include "common.hpp"
@@ -15,6 +16,17 @@ __device__ __forceinline__ void lse_push(Lse& a, float v) {
     if (v > a.m) { a.s = a.s * expf(a.m - v) + 1.f; a.m = v; } else { a.s += expf(v - a.m); }
 }
 
+// log_softmax(x)_c = (x_c - m) - ls with m = max x and ls = log sum exp(x - m): both terms are small wherever the softmax weight is
+// not.  x_c - (m + ls) rounds the normaliser to half an ulp of the largest logit (7.6e-6 at |logit| = 160), and the KL of two heads
+// that agree -- 1e-2 and less -- is a difference of two such terms.
+struct Lsm { float m, ls; };
+__device__ __forceinline__ Lsm lsm_norm(const float* __restrict__ a, int C, int HW) {
+    float m = -INFINITY, s = 0.f;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, a[(size_t)c * HW]);
+    for (int c = 0; c < C; ++c) s += expf(a[(size_t)c * HW] - m);
+    return Lsm{m, logf(s)};
+}
+
 __global__ __launch_bounds__(256) void kld_fwd_kernel(const float* __restrict__ d1, const float* __restrict__ d2, int C, int HW,
                                                       float* __restrict__ kld, int64_t total) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -22,12 +34,10 @@ __global__ __launch_bounds__(256) void kld_fwd_kernel(const float* __restrict__ 
     const int n = (int)(idx / HW), p = (int)(idx - (int64_t)n * HW);
     const float* a = d1 + (size_t)n * C * HW + p;
     const float* b = d2 + (size_t)n * C * HW + p;
-    Lse l1{-INFINITY, 0.f}, l2{-INFINITY, 0.f};
-    for (int c = 0; c < C; ++c) { lse_push(l1, a[(size_t)c * HW]); lse_push(l2, b[(size_t)c * HW]); }
-    const float z1 = l1.m + logf(l1.s), z2 = l2.m + logf(l2.s);
+    const Lsm z1 = lsm_norm(a, C, HW), z2 = lsm_norm(b, C, HW);
     float k = 0.f;
     for (int c = 0; c < C; ++c) {
-        const float av = a[(size_t)c * HW] - z1, bv = b[(size_t)c * HW] - z2;
+        const float av = (a[(size_t)c * HW] - z1.m) - z1.ls, bv = (b[(size_t)c * HW] - z2.m) - z2.ls;
         const float p1 = expf(av);
         k += p1 * av - p1 * bv;
     }
@@ -44,18 +54,16 @@ __global__ __launch_bounds__(256) void kld_bwd_kernel(const float* __restrict__ 
     const size_t base = (size_t)n * C * HW + p;
     const float* a = d1 + base;
     const float* b = d2 + base;
-    Lse l1{-INFINITY, 0.f}, l2{-INFINITY, 0.f};
-    for (int c = 0; c < C; ++c) { lse_push(l1, a[(size_t)c * HW]); lse_push(l2, b[(size_t)c * HW]); }
-    const float z1 = l1.m + logf(l1.s), z2 = l2.m + logf(l2.s);
+    const Lsm z1 = lsm_norm(a, C, HW), z2 = lsm_norm(b, C, HW);
     float k = 0.f;
     for (int c = 0; c < C; ++c) {
-        const float av = a[(size_t)c * HW] - z1, bv = b[(size_t)c * HW] - z2;
+        const float av = (a[(size_t)c * HW] - z1.m) - z1.ls, bv = (b[(size_t)c * HW] - z2.m) - z2.ls;
         const float p1 = expf(av);
         k += p1 * av - p1 * bv;
     }
     const float g = gk[idx];
     for (int c = 0; c < C; ++c) {
-        const float av = a[(size_t)c * HW] - z1, bv = b[(size_t)c * HW] - z2;
+        const float av = (a[(size_t)c * HW] - z1.m) - z1.ls, bv = (b[(size_t)c * HW] - z2.m) - z2.ls;
         const float p1 = expf(av), p2 = expf(bv);
         if (g1) g1[base + (size_t)c * HW] = g * p1 * ((av - bv) - k);
         if (g2) g2[base + (size_t)c * HW] = g * (p2 - p1);

@@ -177,7 +177,7 @@ def soft_arg_max(A, beta=500.0, epsilon=1e-12):
     A_max = torch.max(A, dim=1, keepdim=True)[0]
     A_exp = torch.exp((A - A_max) * beta)
     A_softmax = A_exp / (torch.sum(A_exp, dim=1, keepdim=True) + epsilon)
-    indices = torch.arange(start=0, end=A.size(1)).float().reshape(1, A.size(1), 1, 1)
+    indices = torch.arange(start=0, end=A.size(1)).to(A.dtype).reshape(1, A.size(1), 1, 1)      # (.float() there; float64 for a float64 oracle)
     return F.conv2d(A_softmax, indices)
 
 
@@ -192,7 +192,7 @@ def nid_loss(camera, label, image_bin=16, label_bin=4, bw_camera=0.005, bw_label
     cam_1d = cam.reshape(batch, -1)
     lab_1d = lab.reshape(batch, -1)
     L_c, L_l = 1 / K, 1
-    P_c, P_l = [], [torch.zeros(num_pixel) for _ in range(C)]
+    P_c, P_l = [], [torch.zeros(num_pixel, dtype=cam.dtype) for _ in range(C)]
     for k in range(K):
         mu = L_c * (k + 1 / 2)
         P_c.append(torch.sum(torch.sigmoid((cam_1d - mu + L_c / 2) / bw_camera) - torch.sigmoid((cam_1d - mu - L_c / 2) / bw_camera), 0))

@@ -44,7 +44,10 @@ def test_config2_self_label_pass_bs16_288x480():
     assert lab.shape == (16, 288, 480) and lab.dtype == torch.uint8 and kld.shape == (16, 288, 480)
     assert int(eager.hist.sum()) == 16 * 288 * 480                       # every pixel counted once
     np.testing.assert_array_equal(eager.hist.cpu().numpy(), np.bincount(lab.cpu().numpy().ravel(), minlength=13))
-    assert torch.isfinite(kld).all() and float(kld.min()) > -1e-5        # a KL divergence
+    print('KL map: min %.3e' % float(kld.min()))
+    # a KL divergence: the measured minimum is +2.3e-2 on this input; below zero only float32 rounding of a zero is allowed (the bound of
+    # the identical-heads cases of tests/test_gpu_confident_logits.py)
+    assert torch.isfinite(kld).all() and float(kld.min()) >= -4 * 2.0 ** -22
     # hipGraph replay == eager, twice (static buffers are reused)
     graphed = uest.SelfLabelPass(m, classes=13, device=DEV, use_graph=True)
     for _ in range(2):

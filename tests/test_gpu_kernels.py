@@ -359,7 +359,9 @@ def test_label_epilogue_fused_upsample_vs_unfused():
     close(r['main_up'], mu, atol=1e-5)
     close(r['aux_up'], au, atol=1e-5)
     p1, lp1, lp2 = F.softmax(mu, 1), F.log_softmax(mu, 1), F.log_softmax(au, 1)
-    close(r['kld'], (p1 * lp1 - p1 * lp2).sum(1), atol=2e-5, rtol=1e-3)
+    kref = (p1 * lp1 - p1 * lp2).sum(1)
+    print('KL map: max |kernel - float32 ATen| %.3e' % float((r['kld'].cpu() - kref).abs().max()))
+    close(r['kld'], kref, atol=8e-6, rtol=1e-3)               # 4 x the 1.9e-6 measured with the centred formula
     prob = F.softmax(mu + 0.5 * au, 1)
     close(r['prob'], prob, atol=1e-6)
     ref = np.argmax(prob.numpy().transpose(0, 2, 3, 1), axis=3).astype(np.uint8)
@@ -396,7 +398,9 @@ def test_label_epilogue_hist_equals_epilogue_plus_merge(cfg):
         ref = lut.cpu().numpy()[ref]
     assert np.array_equal(one['labels'].cpu().numpy()[sure], ref.astype(np.uint8)[sure]) and sure.mean() > 0.99
     p1, lp1, lp2 = F.softmax(mu, 1), F.log_softmax(mu, 1), F.log_softmax(au, 1)
-    close(one['kld'], (p1 * lp1 - p1 * lp2).sum(1), atol=3e-5, rtol=1e-3)
+    kref = (p1 * lp1 - p1 * lp2).sum(1)
+    print('KL map %s: max |kernel - float32 ATen| %.3e' % (cfg, float((one['kld'].cpu() - kref).abs().max())))
+    close(one['kld'], kref, atol=2e-5, rtol=1e-3)             # 4 x the 2.9e-6 measured (the 24-class case), one digit up
     assert torch.equal(h1 - 3, h2) and int(h2.sum()) == N * H * W
     np.testing.assert_array_equal(h2.cpu().numpy(), np.bincount(lab2.cpu().numpy().ravel(), minlength=ncls))
     only = ops.label_epilogue_hist(main, None, (H, W), h1, ncls, lut=lut)                  # single-head nets, no KL map

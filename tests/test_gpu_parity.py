@@ -192,6 +192,9 @@ def test_uncertainty_estimator_vs_reference(C, golden):
     d1 = (synth_input((2, C, 12, 20), 50 + C) * 3).to(DEV)
     d2 = (synth_input((2, C, 12, 20), 70 + C) * 3).to(DEV)
     r = ops.label_epilogue(d1, d2, (12, 20), want_prob=True, want_kld=True, want_logits=True)
+    print('KL map C=%d: max |kernel - reference| %.3e' % (C, float((r['kld'].cpu() - torch.from_numpy(g['kld_C%d' % C])).abs().max())))
+    # measured with the centred formula: 1.9e-6 / 2.9e-6 / 3.8e-6 at C = 5 / 13 / 20 (KL up to ~50 here: one to two ulp of the value);
+    # 4 x that is above today's bound, which therefore stays
     torch.testing.assert_close(r['kld'].cpu(), torch.from_numpy(g['kld_C%d' % C]), rtol=1e-4, atol=1e-5)
     torch.testing.assert_close(r['prob'].cpu(), torch.from_numpy(g['prob_C%d' % C]), rtol=1e-4, atol=1e-6)
     assert torch.equal(r['main_up'], d1) and torch.equal(r['aux_up'], d2)      # same-size bilinear is the identity
