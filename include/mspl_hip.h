@@ -527,6 +527,29 @@ int mspl_ce_meters_fwd(const float* pred, const int64_t* target, const float* cl
                        int32_t C, int32_t HW, int32_t miou_classes, double* sums, unsigned long long* areas, void* stream);
 int mspl_ce_flood_finalize(double* sums, float flood_level, int32_t batch_images, float* out3, double* meter, void* stream);
 
+/* The loss, meters and logit gradient of one train_seg iteration (utilities/train_eval_seg.py:44-47 `loss = criterion(outputs,
+ * target).mean()` [no flooding], :57 `miou_class.get_iou(outputs, target)`) for a single-head model, taken from the decoder's
+ * low-resolution head (N,C,Hm,Wm) BEFORE the final F.interpolate(mode='bilinear', align_corners=True) to the label map (N,H,W) of
+ * model/segmentation/espnetv2.py and espdnet.py: the up-sampling happens inside the kernel (mspl_resize_bilinear's expression),
+ * full-size logits are never written.
+ *     sums[0] += sum_valid w[t] * (log S - (o_t - m)),  sums[1] += sum_valid w[t]      (valid: 0 <= t < C and t != ignore_index;
+ *         class_weights NULL = 1; doubles, one atomic pair per workgroup)
+ *     areas[0..3K) += [area_inter | area_pred | area_mask] of MIOU(K).get_iou(up(head), target): first maximum, the uint8 arithmetic of
+ *         utilities/metrics/segmentation_miou.py:28-41; K = miou_classes (1..64); areas may be NULL (no histograms)
+ *     ghead_full (N,C,H,W), may be NULL (forward only): w[t] * (softmax(o)_c - [c == t]), zeros at invalid pixels, overwritten --
+ *         the gradient of sums[0], NOT divided by sums[1]: hand it to mspl_bilinear_bwd and multiply the (N,C,Hm,Wm) result by
+ *         upstream / sums[1] for nn.CrossEntropyLoss's gradient.
+ * sums and areas are ACCUMULATED into (caller zeroes); mspl_ce_flood_finalize with flood_level 0 turns sums into the loss
+ * (|l - 0| + 0 == l in fp32), adds loss * n to the epoch's meter and clears sums.
+ * mspl_ce_head_supported(C): 1 for the class counts built (1..8, 13, 20).  mspl_ce_head_fits(...): 1 when the launcher's own plan
+ * accepts the whole geometry (class count, head no larger than the label map, the head's patch of a band within LDS); the launch
+ * returns MSPL_ERR_UNSUPPORTED otherwise, before anything runs (callers then take mspl_resize_bilinear + mspl_ce_meters_fwd). */
+int mspl_ce_head_supported(int32_t C);
+int mspl_ce_head_fits(int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t H, int32_t W);
+int mspl_ce_head_meters_fwd_bwd(const float* head, const int64_t* target, const float* class_weights, int32_t ignore_index,
+                                int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t H, int32_t W, int32_t miou_classes,
+                                double* sums, unsigned long long* areas, float* ghead_full, void* stream);
+
 /* Stand-alone loss modules (callers that compose them themselves instead of the fused K11 form):
  *  PixelwiseKLD.forward (loss_fns/segmentation_loss.py:181-189): kld (N,HW) = sum_c softmax(d1)*(log_softmax(d1)-log_softmax(d2));
  *  its backward: gd1/gd2 (N,C,HW) from gkld (N,HW); either output may be NULL. */

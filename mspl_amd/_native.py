@@ -153,6 +153,9 @@ SIGNATURES = {
     'mspl_eval_batch_finalize': [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p],
     'mspl_ce_meters_fwd': [c_f32p, ctypes.c_void_p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     'mspl_ce_flood_finalize': [ctypes.c_void_p, ctypes.c_float, c_i32, c_f32p, ctypes.c_void_p, ctypes.c_void_p],
+    'mspl_ce_head_supported': [c_i32],
+    'mspl_ce_head_fits': [c_i32] * 6,
+    'mspl_ce_head_meters_fwd_bwd': [c_f32p, ctypes.c_void_p, c_f32p] + [c_i32] * 8 + [ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_void_p],
     'mspl_miou_areas_fwd': [c_f32p, ctypes.c_void_p, ctypes.c_void_p, c_i32, c_i32, c_i32, c_i32, ctypes.c_void_p, ctypes.c_void_p],
     'mspl_resample_ksize': [c_i32, c_i32],
     'mspl_resample_coeffs': [c_i32, c_i32, ctypes.c_void_p, ctypes.c_void_p],

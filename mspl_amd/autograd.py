@@ -1485,3 +1485,64 @@ def flooded_ce_meters(outputs, target, cw, ignore_idx, b, meters=None):
     (int64[3 * classes]), `meter` (float64[2]) and `sums` (float64[2], zero between steps) on the device, e.g.
     supervised.SupervisedMeters: the same launches add MIOU(classes)'s area histograms of `outputs` and loss * batch size."""
     return FloodedCEMetersFn.apply(outputs, target, cw, ignore_idx, b, meters)
+
+
+def ce_head_fits(head, target):
+    """True when mspl_ce_head_meters_fwd_bwd takes this geometry: the launcher's own plan on (N, C, Hm, Wm, H, W), before any launch."""
+    N, C, Hm, Wm = head.shape
+    H, W = target.shape[-2:]
+    return bool(lib.mspl_ce_head_fits(int(N), int(C), int(Hm), int(Wm), int(H), int(W)))
+
+
+class CEHeadMetersFn(torch.autograd.Function):
+    """`loss = criterion(outputs, target).mean(); miou_class.get_iou(outputs, target); losses.update(loss.item(), n)` of train_seg
+    (utilities/train_eval_seg.py:44-58; no flooding) for SegmentationLoss('ce') on `outputs = up(head)`, from the low-resolution head:
+    mspl_ce_head_meters_fwd_bwd reads the head once for the cross-entropy sums, the area histograms and the unnormalised logit
+    gradient at label resolution; mspl_ce_flood_finalize with b = 0 (`|l - 0| + 0 == l` in fp32) divides, adds loss * n to the
+    epoch's meter and clears the sums.  Backward: mspl_bilinear_bwd of the stored gradient and one multiply of the head-sized
+    result by upstream / sum of valid weights, a device scalar (the transposed interpolation is linear)."""
+
+    @staticmethod
+    def forward(ctx, head, target, cw, ignore_idx, meters):
+        head = _c(head)
+        N, C, Hm, Wm = head.shape
+        target = _c(target.to(torch.int64))
+        if not target.is_cuda or target.dim() != 3 or target.shape[0] != N:
+            raise RuntimeError('mspl_amd: target must be a CUDA tensor (%d, H, W), got %s' % (N, tuple(target.shape)))
+        H, W = target.shape[1:]
+        cw = None if cw is None else _c(cw.float())
+        out3 = torch.empty(3, device=head.device, dtype=torch.float32)
+        # (no_grad, or a head that needs no gradient: the forward-only launch)
+        gfull = torch.empty((N, C, H, W), device=head.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        if meters is None:
+            sums, areas, meter, K = torch.zeros(2, device=head.device, dtype=torch.float64), None, None, 1
+        else:
+            # (meters.sums is zero on entry: the finalize launch of the step before cleared it)
+            sums, areas, meter, K = meters.sums, meters.areas, meters.meter, int(meters.classes)
+        check(lib.mspl_ce_head_meters_fwd_bwd(_p(head), _p(target), _p(cw), int(ignore_idx), N, C, Hm, Wm, H, W, K, _p(sums), _p(areas),
+                                              _p(gfull), _stream()))
+        check(lib.mspl_ce_flood_finalize(_p(sums), 0.0, N, _p(out3), _p(meter), _stream()))
+        ctx.save_for_backward(gfull, out3)
+        ctx.shape = tuple(head.shape)
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        gfull, out3 = ctx.saved_tensors
+        N, C, Hm, Wm = ctx.shape
+        gx = torch.empty(ctx.shape, device=gfull.device, dtype=torch.float32)
+        check(lib.mspl_bilinear_bwd(_p(gfull), N, C, Hm, Wm, gfull.shape[2], gfull.shape[3], _p(gx), _stream()))
+        gx.mul_(grad_out.to(torch.float32) / out3[2])
+        return gx, None, None, None, None
+
+
+def ce_head_meters(head, target, cw, ignore_idx, meters=None, fused=None):
+    """CrossEntropyLoss(cw, ignore_idx)(bilinear(head, target.shape[-2:]), target) of the (N,C,Hm,Wm) head of a single-head model,
+    with the meters of flooded_ce_meters.  fused: None takes the one-launch head-resolution kernel wherever it fits the whole geometry
+    (ce_head_fits) and the form built from bilinear + flooded_ce_meters(b = 0) otherwise (pascal's 21 classes, a patch beyond LDS, a
+    head larger than the label map); False always takes that form; True raises where the kernel does not fit."""
+    if fused is None:
+        fused = ce_head_fits(head, target)
+    if fused:
+        return CEHeadMetersFn.apply(head, target, cw, ignore_idx, meters)
+    return flooded_ce_meters(bilinear(head, tuple(int(v) for v in target.shape[-2:])), target, cw, ignore_idx, 0.0, meters)

@@ -96,8 +96,9 @@ def install_dropin(force=False, script=None, train_loops=False):
     (mspl_amd.script.patch_script; call after the script's own definitions).  train_loops=True also rebinds the script's `train`
     to the loop on the graphed training step (mspl_amd.script.train) and, independently of `script`, puts `train_seg_ue`
     (mspl_amd.script.train_seg_ue, the supervised loop on the graphed supervised step that train_segmentation.py:368 binds) into the
-    `utilities.train_eval_seg` alias beside `val_seg_ue`; the default leaves `train_seg_ue` to the overlay (the reference's own
-    function)."""
+    `utilities.train_eval_seg` alias beside `val_seg_ue`, together with the single-head loops `train_seg` (mspl_amd.script.train_seg,
+    train_segmentation.py:370 for `--model espnetv2` / `espdnet`) and `val_seg` (mspl_amd.evaluation.val_seg); the default leaves
+    `train_seg_ue`, `train_seg` and `val_seg` to the overlay (the reference's own functions)."""
     from . import layers as L, models as M, uest as U
     names = ['nn_layers', 'model', 'loss_fns']
     if not force:
@@ -135,8 +136,8 @@ def install_dropin(force=False, script=None, train_loops=False):
     _alias('utilities.metrics.segmentation_miou', MIOU=Q.MIOU)
     from . import evaluation as E
     if train_loops:
-        from .script import train_seg_ue
-        _alias('utilities.train_eval_seg', val_seg_ue=E.val_seg_ue, train_seg_ue=train_seg_ue)
+        from .script import train_seg, train_seg_ue
+        _alias('utilities.train_eval_seg', val_seg_ue=E.val_seg_ue, train_seg_ue=train_seg_ue, train_seg=train_seg, val_seg=E.val_seg)
     else:
         _alias('utilities.train_eval_seg', val_seg_ue=E.val_seg_ue)
     _alias('loss_fns.segmentation_loss', PixelwiseKLD=S.PixelwiseKLD,

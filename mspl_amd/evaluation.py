@@ -276,12 +276,31 @@ class PipelinedEvalPass(EvalSums):
                 depth = torch.cat([b[1] for b in staged]) if staged[0][1] is not None else None
             lane(images, labels, depth, splits=splits)
 
+    def release(self):
+        """Destroy the lanes' graphs now (nothing may be in flight or staged: call after `result()` / `sums()`).  A pass dropped with
+        its graphs alive leaves their destruction to whenever the object is collected, and a graph must not be destroyed while a
+        stream captures: HIP refuses it, and from a destructor that ends the process."""
+        self._join()
+        for l in self.lanes:
+            l.invalidate_graphs()
+
     def sums(self):
         self._join()
         total = self.lanes[0].sums()
         for l in self.lanes[1:]:
             total = total + l.sums()
         return total
+
+
+def _release(ep, given):
+    """The loops below build a pass per call: its graphs are destroyed before the call returns, while nothing captures (a pass the
+    caller handed in is the caller's)."""
+    if given is None:
+        if isinstance(ep, PipelinedEvalPass):
+            ep.release()
+        else:
+            torch.cuda.synchronize(ep.device)
+            ep.invalidate_graphs()
 
 
 def val_seg_ue(model, dataset_loader, criterion=None, num_classes=21, device='cuda', use_depth=False, add_criterion=None,
@@ -313,12 +332,83 @@ def val_seg_ue(model, dataset_loader, criterion=None, num_classes=21, device='cu
         ep = EvalPass(model, num_classes, class_weights=cw, ignore_idx=255 if ign is None else ign, aux_weight=0.5, device=device,
                       use_graph=use_graph)
     rank, world = mdist.world()
-    for b, batch in enumerate(dataset_loader):
-        if world > 1 and not pre_sharded and b % world != rank:
-            continue
-        ep(batch[0], batch[1], batch[2] if use_depth else None)
-    iou, loss = ep.result()
+    try:
+        for b, batch in enumerate(dataset_loader):
+            if world > 1 and not pre_sharded and b % world != rank:
+                continue
+            ep(batch[0], batch[1], batch[2] if use_depth else None)
+        iou, loss = ep.result()
+    finally:
+        _release(ep, _eval_pass)
     return iou, (loss if criterion is not None else 0)
+
+
+def _val_seg_restated(model, dataset_loader, criterion, num_classes, device, use_depth, add_criterion, rank, world, pre_sharded):
+    """The reference body (utilities/train_eval_seg.py:106-137) on the drop-in modules, for an additional criterion: `loss +=
+    add_criterion(inputs, outputs)` WITHOUT a weight (:123-124).  The meters stay on the device; per rank (no all-reduce)."""
+    from collections import OrderedDict
+    from .training import TrainMeters
+    meters = TrainMeters(num_classes - 1, device)
+    model.eval()
+    with torch.no_grad():
+        for b, batch in enumerate(dataset_loader):
+            if world > 1 and not pre_sharded and b % world != rank:
+                continue
+            inputs = batch[0].to(device=device)
+            target = batch[1].to(device=device)
+            outputs = model(inputs, batch[2].to(device=device)) if use_depth else model(inputs)
+            if isinstance(outputs, OrderedDict):
+                outputs = outputs['out']
+            loss = torch.zeros((), device=inputs.device)
+            if criterion:
+                loss = criterion(outputs, target).mean() + add_criterion(inputs, outputs)
+            meters.add(outputs, target, loss, inputs.size(0))
+            meters.count(inputs.size(0))
+    r = meters.read()
+    return r['inter'] / (r['union'] + 1e-10), r['loss_avg']
+
+
+def val_seg(model, dataset_loader, criterion=None, num_classes=21, device='cuda', use_depth=False, add_criterion=None,
+            greenhouse_use_trav=False, use_graph=True, pre_sharded=False, _eval_pass=None, lanes=3, group=2):
+    """Drop-in for utilities/train_eval_seg.py:93-162, the evaluation loop of the single-head models (`--model espnetv2` /
+    `espdnet`): returns (miou, average loss) ((miou, 0) without a criterion) with the SCALAR miou of :150-155 -- `iou.mean() * 100`
+    with greenhouse_use_trav, else `iou[[1, 2, 3]].mean() * 100`, an IndexError for num_classes - 1 < 4 as there.  (val_seg_ue
+    returns the iou array instead.)
+
+    The batches run on EvalPass / PipelinedEvalPass in eval() mode with aux_weight = 0: criterion and MIOU on the one head, taken at
+    head resolution.  criterion, sharding, lanes and group as in val_seg_ue.  add_criterion takes the reference's per-batch body on
+    the drop-in modules (`loss += add_criterion(inputs, outputs)`, no weight), eagerly and per rank."""
+    rank, world = mdist.world()
+    if add_criterion is not None and criterion and _eval_pass is None:
+        iou, loss = _val_seg_restated(model, dataset_loader, criterion, num_classes, device, use_depth, add_criterion, rank, world,
+                                      pre_sharded)
+        return miou_percent(iou, greenhouse_use_trav), loss
+    cw = ign = None
+    if criterion is not None:
+        if getattr(criterion, 'loss_type', 'ce') != 'ce':
+            raise NotImplementedError("mspl_amd: only loss_type='ce' is on the path")
+        cw = getattr(criterion, 'class_wts', None)
+        if cw is None:
+            cw = getattr(criterion, 'class_weights', None)
+        ign = getattr(criterion, 'ignore_idx', 255)
+    # (_eval_pass: an EvalSums stand-in with EvalPass's call signature, for host-logic tests without a GPU)
+    if _eval_pass is not None:
+        ep = _eval_pass
+    elif use_graph and lanes > 1:
+        ep = PipelinedEvalPass(model, num_classes, depth=lanes, group=group, class_weights=cw, ignore_idx=255 if ign is None else ign,
+                               aux_weight=0.0, device=device)
+    else:
+        ep = EvalPass(model, num_classes, class_weights=cw, ignore_idx=255 if ign is None else ign, aux_weight=0.0, device=device,
+                      use_graph=use_graph)
+    try:
+        for b, batch in enumerate(dataset_loader):
+            if world > 1 and not pre_sharded and b % world != rank:
+                continue
+            ep(batch[0], batch[1], batch[2] if use_depth else None)
+        iou, loss = ep.result()
+    finally:
+        _release(ep, _eval_pass)
+    return miou_percent(iou, greenhouse_use_trav), (loss if criterion is not None else 0)
 
 
 def miou_percent(iou, use_traversable=False):

@@ -15,6 +15,11 @@ reference does not have: `label_batch_size` (default 16; the reference's loader 
 so the maps do not depend on it), `label_in_flight` (3), `label_batches_per_launch` (2).  The arguments the reference functions
 accept and never use (`tgt_num`, `label_2_id`, `valid_labels`, `class_encoding`, `writer`; the ScoreUpdater built at :733 is
 reset and dropped) are accepted and ignored.
+
+The epoch loops of train_segmentation.py live in utilities/train_eval_seg.py and are imported by the script, so install_dropin(
+train_loops=True) can alias them: `train_seg_ue` (:164-247, the two-head espdnetue) and `train_seg` (:16-91, the single-head
+`--model espnetv2` / `espdnet`) below, both on supervised.GraphedSupervisedStep with the meters on the device; their evaluation
+halves `val_seg_ue` / `val_seg` are in mspl_amd.evaluation.
 """
 import torch
 
@@ -271,8 +276,9 @@ def _supervised_fast_path(model, criterion, optimizer, add_criterion, device, us
         return False
 
 
-def _train_seg_ue_fast(model, dataset_loader, optimizer, criterion, device, meters, state):
-    """The step loop on supervised.GraphedSupervisedStep: no .item(), no .cpu(), no synchronize inside.  The caller's SGD never steps
+def _train_seg_ue_fast(model, dataset_loader, optimizer, criterion, device, meters, state, heads=2):
+    """The step loop on supervised.GraphedSupervisedStep (heads=1: its single-head form, for train_seg): no .item(), no .cpu(), no
+    synchronize inside.  The caller's SGD never steps
     (its state stays empty); its groups' hyper-parameters are read into the FlatSGD of the graphed step at every iteration (the
     script writes the learning rates per epoch, train_segmentation.py:353-362).  One graphed step per model is kept on the model
     object and reused across epochs; a new optimizer object starts with zero momentum, as a fresh torch.optim.SGD would."""
@@ -287,8 +293,9 @@ def _train_seg_ue_fast(model, dataset_loader, optimizer, criterion, device, mete
         gs = state.get('step')
         if gs is None:
             # the first batch shapes the capture and is NOT applied by it (consume_first_batch=False)
+            kw = {} if heads == 2 else {'heads': heads}
             gs = supervised.GraphedSupervisedStep(model, inputs, target, criterion, meters=meters, consume_first_batch=False,
-                                                  param_groups=optimizer.param_groups)
+                                                  param_groups=optimizer.param_groups, **kw)
             state['step'] = gs
             state['optimizer'] = None
         if gs.meters is not meters:
@@ -304,8 +311,10 @@ def _train_seg_ue_fast(model, dataset_loader, optimizer, criterion, device, mete
             g['lr'], g['momentum'], g['weight_decay'] = src['lr'], src['momentum'], src['weight_decay']
         if tuple(inputs.shape) == tuple(gs.inputs.shape):
             gs(inputs, target)
-        else:                                                    # the loader has no drop_last: same FlatSGD, same meters, eager
+        elif heads == 2:                                         # the loader has no drop_last: same FlatSGD, same meters, eager
             supervised.train_seg_ue_step(model, inputs, target, criterion, gs.optimizer, b=gs.b, meters=meters)
+        else:
+            supervised.train_seg_step(model, inputs, target, criterion, gs.optimizer, meters=meters, ce_at_head=gs.ce_at_head)
 
 
 def _train_seg_ue_restated(model, dataset_loader, optimizer, criterion, device, use_depth, add_criterion, weight, meters):
@@ -375,3 +384,76 @@ def train_seg_ue(model, dataset_loader, optimizer, criterion, num_classes, epoch
     nid_avg = r['extra_sum'] / r['steps'] if (add_criterion is not None and r['steps']) else 0.0
     print("Epoch: %d[%d steps]\t\tLoss:%.4f\t\tmiou:%.4f\t\tNID loss:%.4f" % (epoch, r['steps'], r['loss_avg'], iou.mean() * 100, nid_avg))
     return iou, r['loss_avg']
+
+
+# ------------------------------------------------------------- train_seg() (utilities/train_eval_seg.py:16-91, train_segmentation.py:370-372)
+def _single_head_fast_path(model, criterion, optimizer, add_criterion, device, use_depth=False):
+    """_supervised_fast_path for the single-head loop: the drop-in ESPNetv2Segmentation or ESPDNetSegmentation, the drop-in
+    SegmentationLoss('ce'), no additional criterion, no depth batch, plain momentum SGD over 2 or 3 groups, a CUDA device."""
+    from . import losses, models
+    if _FORCE_RESTATED or add_criterion is not None or use_depth:
+        return False
+    if type(model) not in (models.ESPNetv2Segmentation, models.ESPDNetSegmentation):
+        return False
+    if type(criterion) is not losses.SegmentationLoss or criterion.loss_type != 'ce':
+        return False
+    if type(optimizer) is not torch.optim.SGD or len(optimizer.param_groups) not in (2, 3):
+        return False
+    for g in optimizer.param_groups:
+        if g.get('dampening', 0) != 0 or g.get('nesterov', False) or g.get('maximize', False):
+            return False
+    try:
+        return torch.device(device).type == 'cuda'
+    except (RuntimeError, TypeError):
+        return False
+
+
+def _train_seg_restated(model, dataset_loader, optimizer, criterion, device, use_depth, add_criterion, weight, meters):
+    """The reference body (:28-69) on the drop-in modules with the caller's own optimizer; the meters stay on the device
+    (`nid_losses.update(loss2.item(), 1)` is the meters' `extra`)."""
+    from . import layers, supervised
+    for batch in dataset_loader:
+        inputs = batch[0].to(device=device)
+        target = batch[1].to(device=device)
+        depth = batch[2].to(device=device) if use_depth else None
+        loss, _ = supervised._single_head_loss(model, inputs, target, depth, criterion, add_criterion, weight, meters)
+        meters.count(inputs.size(0))
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        layers.bump_param_epoch()       # (torch.optim bumps the version counters the caches watch; this covers an optimizer that does not)
+
+
+def train_seg(model, dataset_loader, optimizer, criterion, num_classes, epoch, device='cuda', use_depth=False, add_criterion=None,
+              greenhouse_use_trav=False, weight=1.0):
+    """utilities/train_eval_seg.py:16-91 with its own signature (mind the order of the last two arguments: it is not train_seg_ue's);
+    returns (miou, average loss) with the SCALAR miou of :84-89 -- `iou.mean() * 100` with greenhouse_use_trav, else
+    `iou[[1, 2, 3]].mean() * 100`, an IndexError for num_classes - 1 < 4 as there -- over the epoch's summed areas of the model's one
+    output.  There is no flooding.  With the shipped settings (`_single_head_fast_path`: `--model espnetv2` / `espdnet` without depth,
+    SegmentationLoss('ce'), momentum SGD) the iterations run on supervised.GraphedSupervisedStep(heads=1) with loss, meters and logit
+    gradient taken at the decoder's low-resolution head; the caller's SGD then never steps and holds no state, its groups'
+    hyper-parameters are read every iteration, a partial last batch runs eagerly on the same FlatSGD, and a new optimizer object
+    starts with zero momentum.  Everything else -- RGB-D batches, an additional criterion with `weight`, an OrderedDict output,
+    other models, losses or optimizers -- runs the reference body on the drop-in modules with the caller's optimizer.  Nothing inside
+    the loop synchronises (one device-to-host copy per epoch), so the running log line is not printed.  State on the model object as
+    for train_seg_ue (release_supervised_loop)."""
+    from . import evaluation, supervised
+    model.train()
+    state = model.__dict__.setdefault('_mspl_supervised_loop', {})
+    meters = state.get('meters')
+    if meters is None:
+        meters = state['meters'] = supervised.SupervisedMeters(num_classes - 1, device)       # MIOU(num_classes - 1), :27
+    elif meters.classes != num_classes - 1 or meters.areas.device.type != torch.device(device).type:
+        raise RuntimeError('mspl_amd.script.train_seg: this model was run with num_classes=%d on %s before; call '
+                           'script.release_supervised_loop(model) first' % (meters.classes + 1, meters.areas.device))
+    meters.reset()
+    if _single_head_fast_path(model, criterion, optimizer, add_criterion, device, use_depth):
+        _train_seg_ue_fast(model, dataset_loader, optimizer, criterion, device, meters, state, heads=1)
+    else:
+        _train_seg_restated(model, dataset_loader, optimizer, criterion, device, use_depth, add_criterion, weight, meters)
+    r = meters.read()                   # the epoch's one device-to-host copy
+    iou = r['inter'] / (r['union'] + 1e-10)                                  # :84
+    nid_avg = r['extra_sum'] / r['steps'] if (add_criterion is not None and r['steps']) else 0.0
+    miou = evaluation.miou_percent(iou, greenhouse_use_trav)                 # :86-89
+    print("Epoch: %d[%d steps]\t\tLoss:%.4f\t\tmiou:%.4f\t\tNID loss:%.4f" % (epoch, r['steps'], r['loss_avg'], iou.mean() * 100, nid_avg))
+    return miou, r['loss_avg']

@@ -2,6 +2,8 @@
 uest step.
 
 Reference surface mirrored (paths relative to the reference root):
+  utilities/train_eval_seg.py:16-91     train_seg: the same loop for a model that returns ONE tensor (`--model espnetv2`, `espdnet`):
+                                        loss = criterion(out, target).mean() [+ add_criterion(inputs, out)*weight], NO flooding
   utilities/train_eval_seg.py:164-225   train_seg_ue: model.train() (batch-statistics BatchNorm), loss =
                                         criterion(out + 0.5*aux, target).mean() [+ add_criterion(inputs, out)*weight],
                                         flooding `(loss - b).abs() + b` with b = 0.015 (:221), zero_grad/backward/step
@@ -233,33 +235,100 @@ def _metered_loss(criterion, outputs, target, inputs, add_criterion, weight, b, 
     return loss
 
 
+def _head_loss(model, criterion, add_criterion):
+    """The settings autograd.ce_head_meters computes for a single-head model: the drop-in SegmentationLoss('ce') alone on a model
+    that exposes its low-resolution head."""
+    from . import losses
+    return add_criterion is None and type(criterion) is losses.SegmentationLoss and criterion.loss_type == 'ce' and \
+        hasattr(model, 'forward_lowres')
+
+
+def _single_head_loss(model, inputs, target, depth, criterion, add_criterion, weight, meters, cw=None, ce_at_head=None):
+    """(loss, logits) of one train_seg iteration (utilities/train_eval_seg.py:32-47; no flooding) with `meters` filled when given (the
+    step count stays with the caller).  With SegmentationLoss('ce') alone the loss is taken from `forward_lowres(...)[0]` by
+    autograd.ce_head_meters (ce_at_head: its `fused` argument; None = wherever the kernel fits) and `logits` is that low-resolution
+    head; otherwise the reference's lines on the model's full-size output.  cw: the class-weight tensor the node reads (a graph
+    passes its own static copy)."""
+    from collections import OrderedDict
+    if _head_loss(model, criterion, add_criterion):
+        head = (model.forward_lowres(inputs, depth) if depth is not None else model.forward_lowres(inputs))[0]
+        if cw is None and criterion.class_wts is not None:
+            cw = criterion.class_wts.to(head.device)
+        return ag.ce_head_meters(head, target, cw, int(criterion.ignore_idx), meters, fused=ce_at_head), head
+    outputs = model(inputs, depth) if depth is not None else model(inputs)
+    if isinstance(outputs, OrderedDict):
+        outputs = outputs['out']
+    loss = criterion(outputs, target).mean()
+    loss2 = None
+    if add_criterion is not None:
+        loss2 = add_criterion(inputs, outputs) * weight
+        loss = loss + loss2
+    if meters is not None:
+        meters.add(outputs, target, loss, inputs.shape[0], extra=loss2)
+    return loss, outputs
+
+
+def train_seg_step(model, inputs, target, criterion, optimizer=None, depth=None, add_criterion=None, weight=1.0,
+                   lr=0.009, lr_mult=10.0, momentum=0.9, weight_decay=4e-5, *, meters=None, param_groups=None, ce_at_head=None):
+    """One iteration of train_seg (utilities/train_eval_seg.py:28-69) for a model that returns one tensor (ESPNetv2Segmentation,
+    ESPDNetSegmentation) in train() mode; there is no flooding.  Returns (loss, the logits the loss was taken on, detached -- the
+    low-resolution head with SegmentationLoss('ce') alone, the full-size output otherwise --, optimizer).  optimizer, param_groups
+    and meters as in train_seg_ue_step; ce_at_head as in _single_head_loss."""
+    if optimizer is not None:
+        optimizer.zero_grad()
+    tr = getattr(optimizer, 'transposer', None)
+    with torch.enable_grad(), ag.grad_sinks(), (tr.active() if tr is not None else ag.collect_conv_weights()) as got:
+        layers.prefold_frozen_bn(model)
+        loss, outputs = _single_head_loss(model, inputs, target, depth, criterion, add_criterion, weight, meters, ce_at_head=ce_at_head)
+        loss.backward()
+    if meters is not None:
+        meters.count(inputs.shape[0])
+    if optimizer is None:
+        groups = _sgd_groups(param_groups) if param_groups is not None else segmentation_param_groups(model, lr, lr_mult, depth is not None)
+        optimizer = FlatSGD(groups, lr=lr * lr_mult, momentum=momentum, weight_decay=weight_decay)
+        optimizer.transposer = ag.WeightTransposer(got)      # (after FlatSGD: the parameters now live in its flat buffer)
+    optimizer.all_reduce_grads()
+    optimizer.step()
+    return loss.detach(), outputs.detach(), optimizer
+
+
 class GraphedSupervisedStep:
     """train_seg_ue_step with zero_grad + forward + loss + backward replayed as ONE hipGraph (the iteration is ~900 launches);
     the gradient all-reduce and the SGD kernels (their learning rates change per epoch) stay outside.  The first call runs one
     eager iteration (reveals the gradient-bearing parameters, builds FlatSGD, consumes SGD's first-step rule) and captures;
-    shapes are fixed at construction.  BatchNorm running statistics and num_batches_tracked advance inside the graph."""
+    shapes are fixed at construction.  BatchNorm running statistics and num_batches_tracked advance inside the graph.
+
+    heads=1: the same skeleton around train_seg_step (a single-head model, no flooding: `b` is unused; the loss through
+    _single_head_loss with `ce_at_head`)."""
 
     def __init__(self, model, inputs, target, criterion, depth=None, lr=0.009, lr_mult=10.0, momentum=0.9, weight_decay=4e-5,
-                 b=FLOOD_LEVEL, *, meters=None, consume_first_batch=True, param_groups=None):
+                 b=FLOOD_LEVEL, *, meters=None, consume_first_batch=True, param_groups=None, heads=2, ce_at_head=None):
         """meters: a SupervisedMeters captured inside the graph (the loss then goes through autograd.flooded_ce_meters); it is reset
         when the constructor returns.  param_groups: a caller's torch.optim.SGD groups to build FlatSGD from instead of
         segmentation_param_groups.  consume_first_batch=False: the construction batch only shapes the capture -- the constructor
         takes two SGD steps on it (the eager iteration, then the captured one), and a loop applies each batch exactly once, so
         everything that moved is put back to its value on entry: the parameters, every buffer of the model (BatchNorm
         running_mean, running_var and num_batches_tracked advance in train() mode), a zero momentum buffer and step count."""
+        if heads not in (1, 2):
+            raise ValueError('GraphedSupervisedStep: heads must be 1 or 2')
         self.model, self.criterion, self.b = model, criterion, b
         self.meters = meters
+        self.heads, self.ce_at_head = heads, ce_at_head
         entry = None
         if not consume_first_batch:
             entry = ([p.detach().clone() for p in model.parameters()], dict((n, t.detach().clone()) for n, t in model.named_buffers()))
         self.inputs = inputs.detach().clone()
         self.target = target.detach().clone()
         self.depth = None if depth is None else depth.detach().clone()
-        _, _, self.optimizer = train_seg_ue_step(model, self.inputs, self.target, criterion, None, self.depth, None, 1.0, lr, lr_mult,
-                                                 momentum, weight_decay, b, meters=meters, param_groups=param_groups)
+        if heads == 2:
+            _, _, self.optimizer = train_seg_ue_step(model, self.inputs, self.target, criterion, None, self.depth, None, 1.0, lr, lr_mult,
+                                                     momentum, weight_decay, b, meters=meters, param_groups=param_groups)
+        else:
+            _, _, self.optimizer = train_seg_step(model, self.inputs, self.target, criterion, None, self.depth, None, 1.0, lr, lr_mult,
+                                                  momentum, weight_decay, meters=meters, param_groups=param_groups, ce_at_head=ce_at_head)
         # the class weights the captured loss node reads: a copy of this object's own, refreshed by set_criterion
         self.cw = None
-        if _fused_loss(criterion, None, meters) and criterion.class_wts is not None:
+        if self._node_loss(criterion) and criterion.class_wts is not None:
             self.cw = criterion.class_wts.detach().to(self.inputs.device, torch.float32).clone()
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -267,11 +336,15 @@ class GraphedSupervisedStep:
             self.optimizer.zero_grad()
             with torch.enable_grad(), ag.grad_sinks(), self.optimizer.transposer.active():
                 layers.prefold_frozen_bn(model)
-                self.outputs = two_head_outputs(model, self.inputs, self.depth)
-                if meters is None:
-                    self.loss = flood(criterion(self.outputs, self.target).mean(), b)
+                if heads == 1:
+                    self.loss, self.outputs = _single_head_loss(model, self.inputs, self.target, self.depth, criterion, None, 1.0, meters,
+                                                                cw=self.cw, ce_at_head=ce_at_head)
                 else:
-                    self.loss = _metered_loss(criterion, self.outputs, self.target, self.inputs, None, 1.0, b, meters, cw=self.cw)
+                    self.outputs = two_head_outputs(model, self.inputs, self.depth)
+                    if meters is None:
+                        self.loss = flood(criterion(self.outputs, self.target).mean(), b)
+                    else:
+                        self.loss = _metered_loss(criterion, self.outputs, self.target, self.inputs, None, 1.0, b, meters, cw=self.cw)
                 self.loss.backward()
         self._finish()                                  # the capture did not execute: run the iteration it recorded
         if entry is not None:
@@ -285,12 +358,18 @@ class GraphedSupervisedStep:
         if meters is not None:
             meters.reset()
 
+    def _node_loss(self, criterion):
+        """True when the captured loss is a node that reads this object's own class-weight tensor."""
+        if self.heads == 1:
+            return _head_loss(self.model, criterion, None)
+        return _fused_loss(criterion, None, self.meters)
+
     def set_criterion(self, criterion):
         """Another criterion object of the same kind (a script that rebuilds it): its class weights are copied into the tensor the
         graph reads; anything the capture cannot follow raises."""
         if criterion is self.criterion:
             return
-        if self.meters is None or not _fused_loss(criterion, None, self.meters) or not _fused_loss(self.criterion, None, self.meters):
+        if (self.heads == 2 and self.meters is None) or not self._node_loss(criterion) or not self._node_loss(self.criterion):
             raise RuntimeError('GraphedSupervisedStep: the step was captured with another criterion object')
         if int(criterion.ignore_idx) != int(self.criterion.ignore_idx) or (criterion.class_wts is None) != (self.cw is None):
             raise RuntimeError('GraphedSupervisedStep: the new criterion differs in ignore_idx or in having class weights')
