@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "loss_parts.hpp"
 
 namespace mspl {
 
@@ -46,7 +47,10 @@ __global__ __launch_bounds__(256) void ce_head_kernel(const float* __restrict__ 
                                                       const float* __restrict__ cw, ChGeom g, double* __restrict__ sums,
                                                       unsigned long long* __restrict__ areas, float* __restrict__ gfull) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    __shared__ unsigned int mhist[3 * 64];
+    // (The area counters, the row tally and the sums reduction stay written out here: through loss_parts.hpp's miou_* helpers and
+    // ce_sums_reduce the forward-only <20,true,false> measured 133.8 against 133.1 us at 16 x 20 x 256x480, with the band helpers
+    // alone 133.0.  A change of the rule there is a change here.)
+    __shared__ unsigned int mhist[3 * MIOU_MAX_BINS];
     __shared__ double red[2][4];
     const bool meters = areas != nullptr;
     if (meters) {
@@ -59,23 +63,11 @@ __global__ __launch_bounds__(256) void ce_head_kernel(const float* __restrict__ 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double s_loss = 0.0, s_w = 0.0;
     for (unsigned tile = blockIdx.x; tile < g.total; tile += gridDim.x) {
-        unsigned b = tile;
-        const int txi = b % g.tiles_x;  b /= g.tiles_x;
-        const int tyi = b % g.tiles_y;
-        const int img = b / g.tiles_y;
-        const int y0 = tyi * g.TH, x0 = txi * CH_TW;
-        const int rows = min(g.TH, g.H - y0), cols = min(CH_TW, g.W - x0);
-        // the patch: first source row / column of the band's first pixel .. second source of its last
-        int my0, my1, mx0, mx1, t0, t1;  float f0, f1;
-        bilinear_src(g.sh, y0, g.Hm, my0, t1, f0, f1);              bilinear_src(g.sh, y0 + rows - 1, g.Hm, t0, my1, f0, f1);
-        bilinear_src(g.sw, x0, g.Wm, mx0, t1, f0, f1);              bilinear_src(g.sw, x0 + cols - 1, g.Wm, t0, mx1, f0, f1);
-        const int nmr = min(my1 - my0 + 1, g.MR), nmc = min(mx1 - mx0 + 1, g.MC);     // (the host sized MR, MC from the same rule)
-        // ---- stage the patch: a wave per (channel, row), lanes over the columns
-        for (int cr = wave; cr < C * nmr; cr += 4) {
-            const int c = cr / nmr, r = cr - c * nmr;
-            const float* src = head + (((size_t)img * C + c) * g.Hm + my0 + r) * (size_t)g.Wm + mx0;
-            for (int x = lane; x < nmc; x += 64) sm[c * msz + r * g.MC + x] = src[x];
-        }
+        const BandTile bt = band_tile(tile, g.tiles_x, g.tiles_y, g.TH, CH_TW, g.H, g.W);
+        const int img = bt.img, y0 = bt.y0, x0 = bt.x0, rows = bt.rows;
+        const BandPatch pt = band_patch(g.sh, g.sw, g.Hm, g.Wm, bt, g.MR, g.MC);
+        const int my0 = pt.y0, mx0 = pt.x0, nmr = pt.nr, nmc = pt.nc;
+        band_stage(sm, head, img, C, g.Hm, g.Wm, pt, g.MC, msz, wave, lane);
         __syncthreads();
         for (int r = wave; r < rows; r += 4) {
             const int y = y0 + r;
@@ -184,26 +176,6 @@ __global__ __launch_bounds__(256) void ce_head_kernel(const float* __restrict__ 
             if (mhist[i]) atomicAdd(&areas[i], (unsigned long long)mhist[i]);
 }
 
-// The device's source rule on the host (one fp32 product, floor, clamp: the same values), for exact patch sizes.
-static void ch_src(float scale, int dst, int in_size, int& i0, int& i1) {
-    const float real = scale * (float)dst;
-    int idx = (int)std::floor(real);
-    if (idx > in_size - 1) idx = in_size - 1;
-    i0 = idx;
-    i1 = idx + ((idx < in_size - 1) ? 1 : 0);
-}
-// most source rows (columns) any band of `n` pixels starting at a multiple of n touches
-static int ch_span(float s, int n, int out_size, int in_size) {
-    int most = 1;
-    for (int p = 0; p < out_size; p += n) {
-        int a0, a1, b0, b1;
-        ch_src(s, p, in_size, a0, a1);
-        ch_src(s, std::min(p + n, out_size) - 1, in_size, b0, b1);
-        most = std::max(most, b1 - a0 + 1);
-    }
-    return most;
-}
-
 static bool ch_classes(int C) { return (C >= 1 && C <= 8) || C == 13 || C == 20; }
 
 // The launcher's plan: everything that can refuse a geometry, decided before anything is launched.  Returns MSPL_OK and fills g / lds,
@@ -217,14 +189,10 @@ static int ch_plan(int N, int C, int Hm, int Wm, int H, int W, ChGeom& g, size_t
     g.N = N; g.C = C; g.H = H; g.W = W; g.Hm = Hm; g.Wm = Wm;
     g.sh = bilinear_scale(Hm, H);  g.sw = bilinear_scale(Wm, W);
     g.tiles_x = ceil_div(W, CH_TW);
-    // band height: 8 rows (two per wave) when that still gives ~3 workgroups per CU, else 4; halved while the patch outgrows the budget
-    auto size_for = [&](int th) {
-        g.TH = th;
-        g.MR = ch_span(g.sh, th, H, Hm);  g.MC = ch_span(g.sw, CH_TW, W, Wm) | 1;
-        lds = (size_t)C * (size_t)g.MR * g.MC * sizeof(float);
-    };
-    int th = ((int64_t)N * ceil_div(H, 8) * g.tiles_x >= 768) ? 8 : 4;
-    for (size_for(th); lds > CH_LDS_BUDGET && th > 1; size_for(th)) th >>= 1;
+    g.TH = band_height(N, H, g.tiles_x, CH_LDS_BUDGET, [&](int th) {
+        g.MR = bilinear_span(Hm, H, th);  g.MC = bilinear_span(Wm, W, CH_TW) | 1;
+        return lds = (size_t)C * (size_t)g.MR * g.MC * sizeof(float);
+    });
     if (lds > CH_LDS_BUDGET) { why = "the head's patch does not fit LDS";  return MSPL_ERR_UNSUPPORTED; }
     g.tiles_y = ceil_div(H, g.TH);
     const int64_t tiles = (int64_t)N * g.tiles_y * g.tiles_x;

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "loss_parts.hpp"
 
 namespace mspl {
 
@@ -19,11 +20,10 @@ __global__ __launch_bounds__(256) void ce_meters_kernel(const float* __restrict_
                                                         const float* __restrict__ cw, int ignore, int Crt, int HW, int K,
                                                         int64_t total, double* __restrict__ sums,
                                                         unsigned long long* __restrict__ areas) {
-    __shared__ unsigned int hsh[3 * 64];
-    __shared__ double red[2][4];
+    __shared__ unsigned int hsh[3 * MIOU_MAX_BINS];
     const int C = CT > 0 ? CT : Crt;
     if (areas) {
-        for (int i = threadIdx.x; i < 3 * K; i += 256) hsh[i] = 0;
+        miou_clear(hsh, K);
         __syncthreads();
     }
     // grid-stride with a bounded grid: a workgroup ends with two atomics on the same two addresses (losses.hip, wce_fwd_kernel)
@@ -33,8 +33,7 @@ __global__ __launch_bounds__(256) void ce_meters_kernel(const float* __restrict_
         const float* a = pred + (size_t)n * C * HW + (idx - n * HW);
         const int64_t t64 = target[idx];
         const bool valid = t64 >= 0 && t64 < C && t64 != (int64_t)ignore;
-        // MIOU.get_iou in the reference's uint8 arithmetic (segmentation_miou.py:28-41): +1, 255 wraps to 0 = ignored
-        const unsigned t8 = ((unsigned)(t64 & 255) + 1u) & 255u;
+        const unsigned t8 = miou_label_code(t64);
         if (!valid && (t8 == 0 || !areas)) continue;           // the pixel counts nowhere: its logits are not read
         float lse, ot = 0.f;
         int best = 0;
@@ -64,26 +63,10 @@ __global__ __launch_bounds__(256) void ce_meters_kernel(const float* __restrict_
             s_loss += (double)(w * (lse - ot));
             s_w += (double)w;
         }
-        if (areas) {
-            unsigned p8 = ((unsigned)best + 1u) & 255u;
-            if (t8 == 0) p8 = 0;
-            const unsigned in8 = (p8 == t8) ? p8 : 0u;
-            if (in8 >= 1 && in8 <= (unsigned)K) atomicAdd(&hsh[in8 - 1], 1u);
-            if (p8 >= 1 && p8 <= (unsigned)K) atomicAdd(&hsh[K + p8 - 1], 1u);
-            if (t8 >= 1 && t8 <= (unsigned)K) atomicAdd(&hsh[2 * K + t8 - 1], 1u);
-        }
+        if (areas) miou_count(hsh, K, miou_codes8((unsigned)best, t8));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s_loss += __shfl_down(s_loss, o, 64); s_w += __shfl_down(s_w, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_loss; red[1][threadIdx.x >> 6] = s_w; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(&sums[0], (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]));
-        atomicAdd(&sums[1], (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
-    }
-    if (areas)
-        for (int i = threadIdx.x; i < 3 * K; i += 256)
-            if (hsh[i]) atomicAdd(&areas[i], (unsigned long long)hsh[i]);
+    ce_sums_reduce(s_loss, s_w, sums);
+    if (areas) miou_flush(hsh, K, areas);
 }
 
 // `.mean()` of the one-element loss, the flooding of :221 and AverageMeter.update(loss.item(), n) of :222 in fp32 and the reference's

@@ -270,4 +270,13 @@ static inline float bilinear_scale(int in_size, int out_size) {
     return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.0f;
 }
 
+// Host twin of bilinear_src's index part (one fp32 product, floor, clamp: the same values; the build uses -ffp-contract=off).
+static inline void bilinear_src_host(float scale, int dst, int in_size, int& i0, int& i1) {
+    const float real = scale * (float)dst;
+    int idx = (int)floorf(real);
+    if (idx > in_size - 1) idx = in_size - 1;
+    i0 = idx;
+    i1 = idx + ((idx < in_size - 1) ? 1 : 0);
+}
+
 }  // namespace mspl

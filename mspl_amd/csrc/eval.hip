@@ -6,6 +6,7 @@
 // The reference writes both heads at full resolution (2 * C * H * W floats per image), adds them with an ATen kernel, runs the
 // loss, copies prediction and target to the host and calls torch.histc three times.  Here full-resolution logits never exist.
 #include "common.hpp"
+#include "loss_parts.hpp"
 
 namespace mspl {
 
@@ -21,9 +22,8 @@ __global__ __launch_bounds__(256) void eval_epilogue_kernel(const float* __restr
                                                             const int64_t* __restrict__ target, const float* __restrict__ cw,
                                                             EvGeom g, double* __restrict__ sums, unsigned long long* __restrict__ areas,
                                                             uint8_t* __restrict__ labels) {
-    __shared__ unsigned int hsh[3 * 64];
-    __shared__ double red[2][4];
-    for (int i = threadIdx.x; i < 3 * g.K; i += 256) hsh[i] = 0;
+    __shared__ unsigned int hsh[3 * MIOU_MAX_BINS];
+    miou_clear(hsh, g.K);
     __syncthreads();
     const int x = blockIdx.x * 256 + threadIdx.x;
     const int n = blockIdx.z;
@@ -68,26 +68,11 @@ __global__ __launch_bounds__(256) void eval_epilogue_kernel(const float* __restr
                 s_loss += (double)(wt * ((omax + logf(S)) - ot));
                 s_w += (double)wt;
             }
-            // MIOU.get_iou in the reference's uint8 arithmetic (segmentation_miou.py:28-41): +1, 255 wraps to 0 = ignored
-            unsigned p8 = ((unsigned)best + 1u) & 255u;
-            const unsigned t8 = ((unsigned)(t64 & 255) + 1u) & 255u;
-            if (t8 == 0) p8 = 0;
-            const unsigned in8 = (p8 == t8) ? p8 : 0u;
-            if (in8 >= 1 && in8 <= (unsigned)g.K) atomicAdd(&hsh[in8 - 1], 1u);
-            if (p8 >= 1 && p8 <= (unsigned)g.K) atomicAdd(&hsh[g.K + p8 - 1], 1u);
-            if (t8 >= 1 && t8 <= (unsigned)g.K) atomicAdd(&hsh[2 * g.K + t8 - 1], 1u);
+            miou_count(hsh, g.K, miou_codes((unsigned)best, t64));
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s_loss += __shfl_down(s_loss, o, 64); s_w += __shfl_down(s_w, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_loss; red[1][threadIdx.x >> 6] = s_w; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(&sums[0], (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]));
-        atomicAdd(&sums[1], (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
-    }
-    for (int i = threadIdx.x; i < 3 * g.K; i += 256)
-        if (hsh[i]) atomicAdd(&areas[i], (unsigned long long)hsh[i]);
+    ce_sums_reduce(s_loss, s_w, sums);
+    miou_flush(hsh, g.K, areas);
 }
 
 // AverageMeter.update(loss.item(), n) of the loop (train_eval_seg.py:297) on the device: acc[0] += (sums[0] / sums[1]) * n,

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "loss_parts.hpp"
 
 namespace mspl {
 
@@ -622,8 +623,8 @@ static void launch_merge(int ncls, dim3 grid, hipStream_t st, const MergeSrc& ms
 __global__ __launch_bounds__(256) void miou_areas_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                                          const int64_t* __restrict__ target, int C, int HW, int K,
                                                          int64_t total, unsigned long long* __restrict__ hist) {
-    __shared__ unsigned int h[3 * 64];
-    for (int i = threadIdx.x; i < 3 * K; i += 256) h[i] = 0;
+    __shared__ unsigned int h[3 * MIOU_MAX_BINS];
+    miou_clear(h, K);
     __syncthreads();
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
         unsigned p;
@@ -636,49 +637,15 @@ __global__ __launch_bounds__(256) void miou_areas_kernel(const float* __restrict
         } else {
             p = labels[idx];
         }
-        p = (p + 1u) & 255u;
-        const unsigned t = ((unsigned)(target[idx] & 255) + 1u) & 255u;
-        if (t == 0) p = 0;
-        const unsigned in = (p == t) ? p : 0u;
-        if (in >= 1 && in <= (unsigned)K) atomicAdd(&h[in - 1], 1u);
-        if (p >= 1 && p <= (unsigned)K) atomicAdd(&h[K + p - 1], 1u);
-        if (t >= 1 && t <= (unsigned)K) atomicAdd(&h[2 * K + t - 1], 1u);
+        miou_count(h, K, miou_codes(p, target[idx]));
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 3 * K; i += 256)
-        if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
+    miou_flush(h, K, hist);
 }
 
 }  // namespace mspl
 
 using namespace mspl;
-
-// Host twin of bilinear_src's index part (same fp32 operations; the build uses -ffp-contract=off).
-static void le_host_idx(float scale, int dst, int in_size, int& i0, int& i1) {
-    const float real = scale * (float)dst;
-    int idx = (int)floorf(real);
-    if (idx > in_size - 1) idx = in_size - 1;
-    i0 = idx;
-    i1 = idx + ((idx < in_size - 1) ? 1 : 0);
-}
-
-// Largest number of source positions any tile of `tile` consecutive output positions touches; with align4 the first position
-// is rounded down to a multiple of 4 and the count up to a multiple of 4 (16-byte staging chunks).
-static int le_span(int in_size, int out_size, int tile, bool align4) {
-    const float sc = bilinear_scale(in_size, out_size);
-    int best = 1;
-    for (int o0 = 0; o0 < out_size; o0 += tile) {
-        const int o1 = std::min(o0 + tile, out_size) - 1;
-        int a0, a1, b0, b1;
-        le_host_idx(sc, o0, in_size, a0, a1);
-        le_host_idx(sc, o1, in_size, b0, b1);
-        if (align4) a0 &= ~3;
-        int cnt = b1 - a0 + 1;
-        if (align4) cnt = (cnt + 3) & ~3;
-        best = std::max(best, cnt);
-    }
-    return best;
-}
 
 static int64_t le_blocks(int N, int H, int W) { return (int64_t)ceil_div(W, 256) * (4 * ceil_div(ceil_div(H, LE_RB), 4)) * N; }
 
@@ -706,8 +673,8 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
         // LDS-staged form when the tile's source rows fit (they do for the x2 / x4 heads of the path); else the register form
         LeStage st;
         st.vec = (Wm % 4 == 0) && (!aux || Wa % 4 == 0) && (((uintptr_t)mainp) & 15) == 0 && (((uintptr_t)aux) & 15) == 0;
-        st.nrm = le_span(Hm, H, LE_RB, false);  st.wms = le_span(Wm, W, 256, st.vec);
-        st.nra = aux ? le_span(Ha, H, LE_RB, false) : 0;  st.was = aux ? le_span(Wa, W, 256, st.vec) : 4;
+        st.nrm = bilinear_span(Hm, H, LE_RB, false);  st.wms = bilinear_span(Wm, W, 256, st.vec);
+        st.nra = aux ? bilinear_span(Ha, H, LE_RB, false) : 0;  st.was = aux ? bilinear_span(Wa, W, 256, st.vec) : 4;
         if (!st.vec) { st.wms = (st.wms + 3) & ~3; st.was = (st.was + 3) & ~3; }      // keep the second head's base 16-byte aligned
         st.ncls = hist ? ncls : 0;
         st.magc = (65536u + (unsigned)C - 1) / (unsigned)C;
@@ -796,10 +763,10 @@ extern "C" int mspl_label_epilogue_hist_fits(int32_t N, int32_t C, int32_t Hm, i
     const bool aux = Ha > 0 && Wa > 0;
     if (!(H <= 65535 * LE_RB / 4 && N <= 65535 && (int64_t)N * C * Hm * Wm < (1ll << 31) && (int64_t)N * C * (int64_t)Ha * Wa < (1ll << 31))) return 0;
     const bool vec = (Wm % 4 == 0) && (!aux || Wa % 4 == 0);      // (pointer alignment can only shrink the tile: unaligned = 4-byte staging)
-    const int nrm = le_span(Hm, H, LE_RB, false), nra = aux ? le_span(Ha, H, LE_RB, false) : 0;
-    int wms = le_span(Wm, W, 256, vec), was = aux ? le_span(Wa, W, 256, vec) : 4;
+    const int nrm = bilinear_span(Hm, H, LE_RB, false), nra = aux ? bilinear_span(Ha, H, LE_RB, false) : 0;
+    int wms = bilinear_span(Wm, W, 256, vec), was = aux ? bilinear_span(Wa, W, 256, vec) : 4;
     if (!vec) { wms = (wms + 3) & ~3; was = (was + 3) & ~3; }
-    const int wms4 = (le_span(Wm, W, 256, true) + 3) & ~3, was4 = aux ? (le_span(Wa, W, 256, true) + 3) & ~3 : 4;   // worst case of either staging
+    const int wms4 = (bilinear_span(Wm, W, 256, true) + 3) & ~3, was4 = aux ? (bilinear_span(Wa, W, 256, true) + 3) & ~3 : 4;   // worst case of either staging
     wms = std::max(wms, wms4); was = std::max(was, was4);
     const size_t lds = ((size_t)nrm * C * wms + (size_t)nra * C * was + 32) * sizeof(float);
     return lds <= 128 * 1024 && (nrm + nra) * C < 4096 && wms <= 256 && was <= 256;

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "loss_parts.hpp"
 
 namespace mspl {
 
@@ -90,15 +91,7 @@ __global__ __launch_bounds__(256) void wce_fwd_kernel(const float* __restrict__ 
             den += w;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { num += __shfl_down(num, o, 64); den += __shfl_down(den, o, 64); }
-    __shared__ float part[4][2];
-    if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6][0] = num; part[threadIdx.x >> 6][1] = den; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(&sums[0], (part[0][0] + part[1][0]) + (part[2][0] + part[3][0]));
-        atomicAdd(&sums[1], (part[0][1] + part[1][1]) + (part[2][1] + part[3][1]));
-    }
+    ce_sums_reduce(num, den, sums);
 }
 
 // scale = g[0] * (den ? 1 / den[0] : inv_npix);  gpred_c = scale * w * e^{-u} * (softmax_c - [c == t]);  gu = -scale * w * nll * e^{-u}

@@ -16,6 +16,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "loss_parts.hpp"
 
 namespace mspl {
 
@@ -60,10 +61,8 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
                                                             UhGeom g, float* __restrict__ loss_acc, float* __restrict__ gpred,
                                                             float* __restrict__ gaux, UhMeters mt) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    __shared__ unsigned int mhist[METERS ? 3 * 64 : 1];
-    if (METERS) {
-        for (int i = threadIdx.x; i < 3 * mt.K; i += 256) mhist[i] = 0;       // (ordered before its first use by the tile loop's barrier)
-    }
+    __shared__ unsigned int mhist[METERS ? 3 * MIOU_MAX_BINS : 1];
+    if (METERS) miou_clear(mhist, mt.K);       // (ordered before its first use by the tile loop's barrier)
     const int C = EXACT ? CM : g.C;
     constexpr bool KEEP = CM <= 8;
     constexpr int CK = KEEP ? CM : 1;
@@ -73,31 +72,13 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float contrib = 0.f;
     for (unsigned tile = blockIdx.x; tile < g.total; tile += gridDim.x) {
-        unsigned b = tile;
-        const int txi = b % g.tiles_x;  b /= g.tiles_x;
-        const int tyi = b % g.tiles_y;
-        const int img = b / g.tiles_y;
-        const int y0 = tyi * g.TH, x0 = txi * UH_TW;
-        const int rows = min(g.TH, g.H - y0), cols = min(UH_TW, g.W - x0);
-        // patches: first source row / column of the band's first pixel .. second source of its last
-        int my0, my1, mx0, mx1, ay0, ay1, ax0, ax1, t0, t1;  float f0, f1;
-        bilinear_src(g.shm, y0, g.Hm, my0, t1, f0, f1);              bilinear_src(g.shm, y0 + rows - 1, g.Hm, t0, my1, f0, f1);
-        bilinear_src(g.swm, x0, g.Wm, mx0, t1, f0, f1);              bilinear_src(g.swm, x0 + cols - 1, g.Wm, t0, mx1, f0, f1);
-        bilinear_src(g.sha, y0, g.Ha, ay0, t1, f0, f1);              bilinear_src(g.sha, y0 + rows - 1, g.Ha, t0, ay1, f0, f1);
-        bilinear_src(g.swa, x0, g.Wa, ax0, t1, f0, f1);              bilinear_src(g.swa, x0 + cols - 1, g.Wa, t0, ax1, f0, f1);
-        const int nmr = min(my1 - my0 + 1, g.MR), nmc = min(mx1 - mx0 + 1, g.MC);     // (the host sized MR.. from the same rule)
-        const int nar = min(ay1 - ay0 + 1, g.AR), nac = min(ax1 - ax0 + 1, g.AC);
-        // ---- stage both patches: a wave per (channel, row), lanes over the columns
-        for (int cr = wave; cr < C * nmr; cr += 4) {
-            const int c = cr / nmr, r = cr - c * nmr;
-            const float* src = mainp + (((size_t)img * C + c) * g.Hm + my0 + r) * (size_t)g.Wm + mx0;
-            for (int x = lane; x < nmc; x += 64) LM[c * msz + r * g.MC + x] = src[x];
-        }
-        for (int cr = wave; cr < C * nar; cr += 4) {
-            const int c = cr / nar, r = cr - c * nar;
-            const float* src = auxp + (((size_t)img * C + c) * g.Ha + ay0 + r) * (size_t)g.Wa + ax0;
-            for (int x = lane; x < nac; x += 64) LA[c * asz + r * g.AC + x] = src[x];
-        }
+        const BandTile bt = band_tile(tile, g.tiles_x, g.tiles_y, g.TH, UH_TW, g.H, g.W);
+        const int img = bt.img, y0 = bt.y0, x0 = bt.x0, rows = bt.rows;
+        const BandPatch pm = band_patch(g.shm, g.swm, g.Hm, g.Wm, bt, g.MR, g.MC);
+        const BandPatch pa = band_patch(g.sha, g.swa, g.Ha, g.Wa, bt, g.AR, g.AC);
+        const int my0 = pm.y0, mx0 = pm.x0, ay0 = pa.y0, ax0 = pa.x0;
+        band_stage(LM, mainp, img, C, g.Hm, g.Wm, pm, g.MC, msz, wave, lane);
+        band_stage(LA, auxp, img, C, g.Ha, g.Wa, pa, g.AC, asz, wave, lane);
         __syncthreads();
         for (int r = wave; r < rows; r += 4) {
             const int y = y0 + r;
@@ -140,10 +121,7 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
 #pragma unroll
                     for (int c = 1; c < CM; ++c)
                         if ((EXACT || c < C) && a[c] > best) { best = a[c];  bi = (unsigned)c; }
-                    const unsigned g8 = ((unsigned)(t & 255) + 1u) & 255u;
-                    const unsigned p8 = g8 ? bi + 1u : 0u;
-                    pk_p |= p8 << (8 * j);
-                    pk_g |= g8 << (8 * j);
+                    miou_pack(pk_p, pk_g, j, miou_codes(bi, t));
                 }
                 float e1[CK], e2[CK], eo[CK];
                 float s1 = 0.f, s2 = 0.f, so = 0.f;
@@ -189,24 +167,7 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
                     }
                 }
             }
-            if (METERS) {
-                const unsigned eq = pk_p ^ pk_g;                        // a zero byte: p == g, the intersection carries p
-                for (unsigned k = 1; k <= (unsigned)mt.K; ++k) {
-                    unsigned ci = 0, cp = 0, cg = 0;                     // wave-uniform
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const bool isp = ((pk_p >> (8 * j)) & 0xffu) == k, isg = ((pk_g >> (8 * j)) & 0xffu) == k;
-                        cp += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(isp));
-                        cg += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(isg));
-                        ci += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(isp && ((eq >> (8 * j)) & 0xffu) == 0u));
-                    }
-                    if (lane == 0) {
-                        if (ci) atomicAdd(&mhist[k - 1], ci);
-                        if (cp) atomicAdd(&mhist[mt.K + k - 1], cp);
-                        if (cg) atomicAdd(&mhist[2 * mt.K + k - 1], cg);
-                    }
-                }
-            }
+            if (METERS) miou_tally_row(mhist, mt.K, pk_p, pk_g, lane);
         }
         __syncthreads();                 // the next tile's staging overwrites the patches
     }
@@ -224,29 +185,8 @@ __global__ __launch_bounds__(256) void uw_loss_heads_kernel(const float* __restr
             atomicAdd(mt.meter, (double)mt.weight * (double)share);
         }
         // (the tile loop's last barrier ordered every wave's LDS adds; a workgroup with no tile has only zeros)
-        for (int i = tid; i < 3 * mt.K; i += 256)
-            if (mhist[i]) atomicAdd(&mt.areas[i], (unsigned long long)mhist[i]);
+        miou_flush(mhist, mt.K, mt.areas);
     }
-}
-
-// The device's source rule on the host (one fp32 product, floor, clamp: the same values), for exact patch sizes.
-static void uh_src(float scale, int dst, int in_size, int& i0, int& i1) {
-    const float real = scale * (float)dst;
-    int idx = (int)std::floor(real);
-    if (idx > in_size - 1) idx = in_size - 1;
-    i0 = idx;
-    i1 = idx + ((idx < in_size - 1) ? 1 : 0);
-}
-// most source rows (columns) any band of `n` pixels starting at a multiple of n touches
-static int uh_span(float s, int n, int out_size, int in_size) {
-    int most = 1;
-    for (int p = 0; p < out_size; p += n) {
-        int a0, a1, b0, b1;
-        uh_src(s, p, in_size, a0, a1);
-        uh_src(s, std::min(p + n, out_size) - 1, in_size, b0, b1);
-        most = std::max(most, b1 - a0 + 1);
-    }
-    return most;
 }
 
 }  // namespace mspl
@@ -275,14 +215,11 @@ static int uh_launch(const float* main_lo, const float* aux_lo, const int64_t* t
     // band height: 8 rows (two per wave) when that still gives ~3 workgroups per CU, else 4; halved while the patches outgrow 64 KB
     // of LDS (four workgroups per CU at C = 5), 128 KB at most (C = 20)
     size_t lds = 0;
-    auto size_for = [&](int th) {
-        g.TH = th;
-        g.MR = uh_span(g.shm, th, H, Hm);  g.MC = uh_span(g.swm, UH_TW, W, Wm) | 1;
-        g.AR = uh_span(g.sha, th, H, Ha);  g.AC = uh_span(g.swa, UH_TW, W, Wa) | 1;
-        lds = (size_t)C * ((size_t)g.MR * g.MC + (size_t)g.AR * g.AC) * sizeof(float);
-    };
-    int th = ((int64_t)N * ceil_div(H, 8) * g.tiles_x >= 768) ? 8 : 4;
-    for (size_for(th); lds + extra > 64 * 1024 && th > 1; size_for(th)) th >>= 1;
+    g.TH = band_height(N, H, g.tiles_x, 64 * 1024 - extra, [&](int th) {
+        g.MR = bilinear_span(Hm, H, th);  g.MC = bilinear_span(Wm, W, UH_TW) | 1;
+        g.AR = bilinear_span(Ha, H, th);  g.AC = bilinear_span(Wa, W, UH_TW) | 1;
+        return lds = (size_t)C * ((size_t)g.MR * g.MC + (size_t)g.AR * g.AC) * sizeof(float);
+    });
     MSPL_REQUIRE(lds <= 128 * 1024, MSPL_ERR_UNSUPPORTED, "uw_loss_heads: patches of %zu bytes do not fit", lds);
     g.tiles_y = ceil_div(H, g.TH);
     const int64_t tiles = (int64_t)N * g.tiles_y * g.tiles_x;
