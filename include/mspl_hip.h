@@ -487,6 +487,31 @@ int mspl_uw_loss_heads_meters_fwd_bwd(const float* main_lo, const float* aux_lo,
 int mspl_dense_conv_fwd(const float* x, const float* w_packed, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W,
                         int32_t ksize, int32_t dilation, const mspl_epilogue_t* ep, float* out, void* stream);
 
+/* K13 backward: what Conv2d autograd computes for the ASPP heads in train() (nn_layers/aspp.py:40-51 / :87-98).
+ *
+ * Weight gradient, in the packed (k*k, Cout, Cin) layout of w_packed (the inverse permute gives (Cout, Cin, k, k) as a view):
+ *     dw_packed[tap][co][ci] = sum over (n, y, x) of gy[n][co][y][x] * x[n][ci][y + dy(tap)][x + dx(tap)]   (zero outside the image)
+ *     dbias[co]              = sum over (n, y, x) of gy[n][co][y][x]      (optional; from the same launch, gy is read once)
+ * gy (N,Cout,H,W), x (N,Cin,H,W) contiguous; both outputs are OVERWRITTEN.  A tap whose shift leaves the image for every pixel
+ * (dilation >= H or >= W in its direction) is written as exact 0.0f.  Cin % 32 == 0, any Cout / N / H / W, dilation >= 1, ksize 1 or
+ * 3; anything else: MSPL_ERR_UNSUPPORTED before a launch.  split: the pixel axis is cut into that many ranges whose partial tiles go
+ * to `workspace` and are added in range order by a second launch (no floating-point atomics: bit-identical from run to run);
+ * 0 = the library chooses, 1 = one range and no workspace, at most 64.  The workspace is the caller's:
+ * mspl_dense_conv_wgrad_workspace_bytes() says how large it must be for the same arguments (0 when one range is used). */
+int64_t mspl_dense_conv_wgrad_workspace_bytes(int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize,
+                                              int32_t dilation, int32_t split);
+int mspl_dense_conv_wgrad(const float* gy, const float* x, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W,
+                          int32_t ksize, int32_t dilation, int32_t split, void* workspace, int64_t workspace_bytes,
+                          float* dw_packed, float* dbias, void* stream);
+/* Data gradient of nbranch (1..4) stride-1, padding = dilation convolutions of ONE input, all added into one gx (N,Cx,H,W):
+ *     gx = sum_b dense_conv(gy[b], wt_packed[b])        wt_packed[b][t][ci][co] = w_packed[b][k*k - 1 - t][co][ci]
+ * as ONE launch of the K13 kernels whose K loop runs over every (gy, weights, dilation) triple (the four spatial ASPP branches:
+ * K = (1 + 27) taps x 256).  gy[b] (N,Cg,H,W); Cg is the convolutions' Cout, Cx their Cin; Cg % 32 == 0 (else
+ * MSPL_ERR_UNSUPPORTED), weights 16-byte aligned.  accumulate != 0: gx += instead of gx =. */
+int mspl_dense_conv_dgrad(const float* const* gy, const float* const* wt_packed, const int32_t* ksize, const int32_t* dilation,
+                          int32_t nbranch, int32_t N, int32_t Cg, int32_t Cx, int32_t H, int32_t W, int32_t accumulate,
+                          float* gx, void* stream);
+
 /* MIOU.get_iou (utilities/metrics/segmentation_miou.py:13-44) on the device: argmax (first maximum) of logits (N,C,HW), or
  * ready labels (N,HW) uint8 (pass exactly one of the two), against int64 targets, in the reference's uint8 arithmetic (+1,
  * 255 wraps to 0 = ignored).  hist: 3*num_classes counters [area_inter | area_pred | area_mask], accumulated into (caller

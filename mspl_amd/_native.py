@@ -148,6 +148,9 @@ SIGNATURES = {
                              [ctypes.POINTER(ctypes.c_void_p)] * 2 + [ctypes.c_void_p],
     'mspl_dense_conv_fwd': [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _EP, c_f32p,
                             ctypes.c_void_p],
+    'mspl_dense_conv_wgrad_workspace_bytes': [c_i32] * 8,
+    'mspl_dense_conv_wgrad': [c_f32p, c_f32p] + [c_i32] * 8 + [ctypes.c_void_p, c_i64, c_f32p, c_f32p, ctypes.c_void_p],
+    'mspl_dense_conv_dgrad': [ctypes.POINTER(ctypes.c_void_p)] * 2 + [ctypes.POINTER(c_i32)] * 2 + [c_i32] * 7 + [c_f32p, ctypes.c_void_p],
     'mspl_eval_epilogue_fwd': [c_f32p, c_f32p, ctypes.c_void_p, c_f32p] + [c_i32] * 8 + [ctypes.c_float, c_i32, c_i32, ctypes.c_void_p,
                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     'mspl_eval_batch_finalize': [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p],
@@ -213,6 +216,7 @@ def _load():
     lib.mspl_eesp_dw_exp_next_pack_floats.restype = ctypes.c_int64
     lib.mspl_label_epilogue_hist_workspace_bytes.restype = ctypes.c_int64
     lib.mspl_train_transform_workspace_bytes.restype = ctypes.c_int64
+    lib.mspl_dense_conv_wgrad_workspace_bytes.restype = ctypes.c_int64
     lib.mspl_png_writer_create.restype = ctypes.c_void_p          # a handle
     lib.mspl_png_writer_submit.restype = ctypes.c_int64           # a ticket (or a negative status)
     lib.mspl_version.restype = ctypes.c_char_p

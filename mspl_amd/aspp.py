@@ -1,18 +1,22 @@
 """nn_layers/aspp.py on the HIP path: `ASPP(num_classes)` (512-channel trunks) and `ASPP_Bottleneck(num_classes)` (2048-channel
 trunks) -- the DeepLabv3 heads of BASELINE configs[4].  Same constructor, attribute names and `state_dict()` as the reference;
-eval-mode BatchNorm only (folded, together with the conv bias, into the producing kernel's epilogue).
+Under torch.no_grad(): eval-mode BatchNorm (folded, together with the conv bias, into the producing kernel's epilogue).
+In train() with gradients enabled: the reference's training forward (batch-statistics BatchNorm, running-statistics update)
+on autograd nodes with HIP backward kernels.  eval() with gradients enabled (frozen-BN fine-tuning of the heads) is refused.
 
     out_1x1   = relu(bn(conv_1x1_1(x)))                       aspp.py:40 / :87
     out_3x3_k = relu(bn(conv_3x3_k(x))),  dilation 6, 12, 18  aspp.py:41-43 / :88-90      <- K13, the matrix-core kernel
     out_img   = interpolate(relu(bn(conv_1x1_2(avg_pool(x)))))  (a constant map: bilinear from 1x1)   :45-47 / :92-94
     out       = conv_1x1_4(relu(bn(conv_1x1_3(cat[...]))))     aspp.py:49-51 / :96-98
 
-The five branches write straight into their channel slice of one (N,1280,H,W) buffer.
+Inference: the five branches write straight into their channel slice of one (N,1280,H,W) buffer.
+Training: each branch keeps its raw convolution output z (what the BatchNorm backward needs); the four convolutions of the
+feature map are ONE autograd node (one data-gradient launch into one gx), torch.cat builds the concatenation.
 """
 import torch
 from torch import nn
 
-from . import ops
+from . import autograd, ops
 from .layers import bn_fold, cached
 from .ops import Epi
 
@@ -54,9 +58,42 @@ class _ASPPBase(nn.Module):
         sc, sh, zero = cached(bn, 'aspp_epi_%s_%d' % (ctot, coff), [bn.weight, bn.bias, bn.running_mean, bn.running_var, conv.bias], build)
         return Epi(sc, sh, zero)
 
+    def _packs(self, conv):
+        """(packed weight, callable giving the data-gradient pack) of a dense convolution, both cached per weight version."""
+        return (self._packed(conv),
+                lambda: cached(conv, 'packed_dgrad', [conv.weight], lambda: ops.pack_dense_weight_dgrad(conv.weight)))
+
+    def _relu(self, z, bn):
+        """relu(bn(z)) with batch statistics: PReLU with a constant zero slope, which takes no gradient."""
+        zero = cached(bn, 'aspp_zero_alpha', [bn.weight], lambda: torch.zeros(bn.num_features, device=bn.weight.device))
+        return autograd.bn_train_prelu(z, bn, alpha=zero)
+
+    def _forward_train(self, feature_map):
+        """nn_layers/aspp.py:40-51 / :87-98 in train(): saved activations are the feature map (once), the five z, the concatenation
+        and conv_1x1_3's z."""
+        H, W = feature_map.shape[2:]
+        spatial = [(self.conv_1x1_1, self.bn_conv_1x1_1), (self.conv_3x3_1, self.bn_conv_3x3_1),
+                   (self.conv_3x3_2, self.bn_conv_3x3_2), (self.conv_3x3_3, self.bn_conv_3x3_3)]
+        zs = autograd.dense_conv_branches(feature_map, [c for c, _ in spatial], [self._packs(c) for c, _ in spatial])
+        outs = [self._relu(z, bn) for z, (_, bn) in zip(zs, spatial)]
+        img = autograd.adaptive_avgpool(feature_map, (1, 1))
+        (zi,) = autograd.dense_conv_branches(img, [self.conv_1x1_2], [self._packs(self.conv_1x1_2)])
+        outs.append(autograd.bilinear(self._relu(zi, self.bn_conv_1x1_2), (int(H), int(W))))
+        cat = torch.cat(outs, 1)
+        (z3,) = autograd.dense_conv_branches(cat, [self.conv_1x1_3], [self._packs(self.conv_1x1_3)])
+        out = self._relu(z3, self.bn_conv_1x1_3)
+        return autograd.conv_bias(out, self.conv_1x1_4)
+
     def forward(self, feature_map):
         if torch.is_grad_enabled():
-            raise RuntimeError('mspl_amd: the ASPP heads are inference-only on the HIP path (call under torch.no_grad())')
+            if not self.training:
+                raise RuntimeError('mspl_amd: the ASPP heads are inference-only in eval() on the HIP path: frozen-BatchNorm '
+                                   'fine-tuning of the heads is not supported (call under torch.no_grad(), or train() the head '
+                                   'for batch-statistics training)')
+            return self._forward_train(feature_map)
+        return self._forward_infer(feature_map)
+
+    def _forward_infer(self, feature_map):
         N, _, H, W = feature_map.shape
         cat = torch.empty((N, 1280, H, W), device=feature_map.device, dtype=torch.float32)
         ops.dense_conv(feature_map, self._packed(self.conv_1x1_1), 1, 1, self._epi(self.conv_1x1_1, self.bn_conv_1x1_1, 1280, 0),

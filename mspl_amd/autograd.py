@@ -327,6 +327,106 @@ def conv_skip(x, w, groups):
     return ConvSkipFn.apply(x, w, groups)
 
 
+class DenseConvFn(torch.autograd.Function):
+    """z_b = Conv2d(x; w_b, bias_b, stride 1, padding = dilation = dil_b), b = 0..n-1: the 1..4 dense convolutions of ONE input that
+    an ASPP head runs on its feature map (nn_layers/aspp.py:40-43 / :87-90), or a single one (n = 1).  Forward: K13 with the conv bias
+    as the epilogue shift.  Backward: ONE data-gradient launch for all branches (K13 on the transposed, tap-reversed weights with
+    the K loop over every branch: the branches add into the same gx, which is written once) -- skipped when x needs no gradient --
+    and one weight + bias gradient launch per branch (mspl_dense_conv_wgrad).  x is saved once for all branches.
+    `packs[b]` = (w_packed, callable -> the data-gradient pack): the module's cached copies."""
+
+    @staticmethod
+    def forward(ctx, x, dils, packs, *wb):
+        x = _c(x)
+        n = len(dils)
+        ws, bs = wb[0::2], wb[1::2]
+        zs = tuple(ops.dense_conv(x, packs[i][0], ws[i].shape[-1], dils[i], Epi(shift=bs[i])) for i in range(n))
+        ctx.save_for_backward(x, *ws)
+        ctx.dils, ctx.wt = tuple(dils), [p[1] for p in packs]
+        ctx.g_w, ctx.g_b = [GradDst(w) for w in ws], [GradDst(b) for b in bs]
+        return zs
+
+    @staticmethod
+    def backward(ctx, *gzs):
+        x, ws = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        n = len(ctx.dils)
+        ks = [w.shape[-1] for w in ws]
+        live = [i for i in range(n) if gzs[i] is not None]
+        gz = {i: _c(gzs[i]) for i in live}
+        gx = None
+        if ctx.needs_input_grad[0] and live:
+            gx = ops.dense_conv_dgrad([gz[i] for i in live], [ctx.wt[i]() for i in live], [ks[i] for i in live],
+                                      [ctx.dils[i] for i in live])
+        grads = []
+        for i in range(n):
+            need_w, need_b = ctx.needs_input_grad[3 + 2 * i], ctx.needs_input_grad[4 + 2 * i]
+            grads += _dense_wgrad(gz[i], x, ks[i], ctx.dils[i], ctx.g_w[i], ctx.g_b[i], need_w, need_b) if i in gz else [None, None]
+        return (gx, None, None, *grads)
+
+
+def _dense_wgrad(gz, x, k, dil, g_w, g_b, need_w, need_b):
+    """[gw, gb] of a dense convolution from ONE mspl_dense_conv_wgrad launch, as `g_w` / `g_b` (GradDst) hand them back.  The kernel
+    overwrites: the bias gradient goes straight to where g_b says unless that is a sink, which is added to; the weight gradient
+    comes out in the packed layout and goes back as its (Cout, Cin, k, k) view (added to a sink)."""
+    gw = gb = None
+    if need_w or need_b:
+        dbuf = g_b.buf(zeroed=False) if (need_b and not g_b.is_sink) else None
+        dw, db = ops.dense_conv_wgrad(gz, x, k, dil, want_bias=need_b, out_bias=dbuf)
+        if need_b:
+            if g_b.is_sink:
+                g_b.sink.add_(db)
+            gb = g_b.result()
+        if need_w:
+            dwv = ops.unpack_dense_weight(dw, k)
+            if g_w.is_sink:
+                g_w.sink.add_(dwv)
+            else:
+                gw = dwv
+    return [gw, gb]
+
+
+class ConvBiasFn(torch.autograd.Function):
+    """y = conv1x1(x, w) + bias for a dense 1x1 convolution with few output channels (an ASPP head's conv_1x1_4: 256 -> classes):
+    the 1x1 forward kernel with the bias as epilogue shift, its data gradient on the same kernel with the transposed weight (as
+    ConvFn), weight and bias gradient from mspl_dense_conv_wgrad (fixed summation order: mspl_conv_bwd_weight adds its pixel
+    ranges with float atomics, and a head's step is bit-reproducible without it)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x, w = _c(x), _c(w)
+        ctx.save_for_backward(x, w)
+        ctx.g_w, ctx.g_b = GradDst(w), GradDst(b)
+        return ops.conv1x1(x, w, 1, Epi(shift=b))
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = _c(gy)
+        gx = ops.conv1x1(gy, _transposed_weights(w, 1, 1), 1) if ctx.needs_input_grad[0] else None
+        return (gx, *_dense_wgrad(gy, x, 1, 1, ctx.g_w, ctx.g_b, ctx.needs_input_grad[1], ctx.needs_input_grad[2]))
+
+
+def conv_bias(x, conv):
+    """conv(x) for an nn.Conv2d(k = 1, groups = 1, bias=True) with Cin % 32 == 0: see ConvBiasFn."""
+    if conv.kernel_size != (1, 1) or conv.groups != 1 or conv.stride != (1, 1) or conv.bias is None:
+        raise RuntimeError('mspl_amd: conv_bias takes Conv2d(k = 1, stride 1, groups = 1, bias=True)')
+    return ConvBiasFn.apply(x, conv.weight, conv.bias)
+
+
+def dense_conv_branches(x, convs, packs):
+    """[conv(x) for conv in convs] for nn.Conv2d modules with groups = 1, stride 1, k in {1, 3}, padding = dilation (k = 3), as one
+    node (DenseConvFn); packs[b] = (packed weight, callable giving the data-gradient pack)."""
+    for c in convs:
+        k = c.kernel_size[0]
+        if c.groups != 1 or c.stride != (1, 1) or c.kernel_size != (k, k) or k not in (1, 3) or c.bias is None or \
+                c.dilation[0] != c.dilation[1] or c.padding != ((0, 0) if k == 1 else c.dilation):
+            raise RuntimeError('mspl_amd: dense_conv takes Conv2d(k = 1 | 3, stride 1, padding = dilation, groups = 1, bias=True)')
+    wb = []
+    for c in convs:
+        wb += [c.weight, c.bias]
+    return DenseConvFn.apply(x, tuple(c.dilation[0] for c in convs), packs, *wb)
+
+
 class EespDwBNFn(torch.autograd.Function):
     """K2 (the four dilated depthwise 3x3 + HFF + cat) and br_after_cat in train() of an EESP block as ONE node (the supervised
     loop; the strided blocks and shapes the fused backward does not cover take mspl_hff_bn_stat_suffix_bwd + mspl_eesp_dw_bwd):

@@ -272,6 +272,67 @@ def dense_conv(x, w_packed, ksize, dilation=1, ep=None, out=None):
     return dst
 
 
+def pack_dense_weight_dgrad(w):
+    """(Cout, Cin, k, k) conv weight -> the (k*k, Cin, Cout) weights of its data gradient as a dense_conv of gy (stride 1,
+    padding = dilation): transposed and tap-reversed, Wt[t][ci][co] = Wp[k*k - 1 - t][co][ci] (a permute copy)."""
+    if w.dim() != 4 or w.shape[2] != w.shape[3] or w.dtype != torch.float32:
+        raise RuntimeError('mspl_amd: pack_dense_weight_dgrad takes a float32 (Cout, Cin, k, k) weight, got %s %s' % (tuple(w.shape), w.dtype))
+    Cout, Cin, k, _ = w.shape
+    return w.flip(2, 3).permute(2, 3, 1, 0).reshape(k * k, Cin, Cout).contiguous()
+
+
+def unpack_dense_weight(wp, ksize):
+    """The inverse permute of pack_dense_weight, as a VIEW: (k*k, Cout, Cin) -> (Cout, Cin, k, k)."""
+    taps, Cout, Cin = wp.shape
+    return wp.view(ksize, ksize, Cout, Cin).permute(2, 3, 0, 1)
+
+
+def dense_conv_wgrad(gy, x, ksize, dilation=1, want_bias=True, split=0, out_bias=None):
+    """Weight and bias gradient of dense_conv: gy (N,Cout,H,W), x (N,Cin,H,W) -> (dw in the packed (k*k, Cout, Cin) layout, db (Cout,)
+    or None).  split: pixel ranges (0: the library chooses); the workspace of a split comes from torch's allocator."""
+    gy, x = _f32(gy, 'gy'), _f32(x, 'x')
+    N, Cin, H, W = x.shape
+    Cout = gy.shape[1]
+    if (gy.shape[0],) + tuple(gy.shape[2:]) != (N, H, W):
+        raise RuntimeError('mspl_amd: dense_conv_wgrad gy %s does not match x %s' % (tuple(gy.shape), tuple(x.shape)))
+    args = (N, Cin, Cout, H, W, int(ksize), int(dilation), int(split))
+    nbytes = int(lib.mspl_dense_conv_wgrad_workspace_bytes(*args))
+    if nbytes < 0:
+        check(nbytes)
+    ws = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32) if nbytes else None
+    dw = torch.empty((ksize * ksize, Cout, Cin), device=x.device, dtype=torch.float32)
+    db = None
+    if want_bias:
+        db = out_bias if out_bias is not None else torch.empty(Cout, device=x.device, dtype=torch.float32)
+    check(lib.mspl_dense_conv_wgrad(_p(gy), _p(x), *args, _p(ws), nbytes, _p(dw), _p(db), _stream()))
+    return dw, db
+
+
+def dense_conv_dgrad(gys, wts, ksizes, dilations, out=None):
+    """Data gradient of 1..4 dense convolutions of one input in ONE launch: gx = sum_b dense_conv(gys[b], wts[b]) with wts[b] from
+    pack_dense_weight_dgrad.  out: an existing (N,Cx,H,W) tensor to ADD to (else a fresh one is written)."""
+    gys = [_f32(g, 'gy') for g in gys]
+    wts = [_f32(w, 'wt_packed') for w in wts]
+    n = len(gys)
+    N, Cg, H, W = gys[0].shape
+    Cx = wts[0].shape[1]
+    for g, w, k in zip(gys, wts, ksizes):
+        if tuple(g.shape) != (N, Cg, H, W) or tuple(w.shape) != (k * k, Cx, Cg):
+            raise RuntimeError('mspl_amd: dense_conv_dgrad gy %s / weights %s do not match (N,%d,%d,%d) / (k*k,%d,%d)'
+                               % (tuple(g.shape), tuple(w.shape), Cg, H, W, Cx, Cg))
+    if out is None:
+        gx = torch.empty((N, Cx, H, W), device=gys[0].device, dtype=torch.float32)
+    else:
+        gx, _ = _dest((out, 0), (N, Cx, H, W), gys[0])
+        if gx.shape[1] != Cx:
+            raise RuntimeError('mspl_amd: dense_conv_dgrad destination %s, expected %d channels' % (tuple(gx.shape), Cx))
+    arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])              # noqa: E731
+    ints = lambda vs: (ctypes.c_int32 * n)(*[int(v) for v in vs])                    # noqa: E731
+    check(lib.mspl_dense_conv_dgrad(arr(gys), arr(wts), ints(ksizes), ints(dilations), n, N, Cg, Cx, H, W, int(out is not None), _p(gx),
+                                    _stream()))
+    return gx
+
+
 def avgpool3x3s2(x, ep=None, out=None, plane_sums=False):
     """3x3 / stride 2 / pad 1 average pool (+ epilogue).  plane_sums=True: returns (pooled, partial sums (N*C, nblk) of x per
     plane) -- for a gate over the same tensor (gate_from_sums) without reading it again."""
