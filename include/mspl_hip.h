@@ -487,6 +487,24 @@ int mspl_uw_loss_heads_meters_fwd_bwd(const float* main_lo, const float* aux_lo,
 int mspl_dense_conv_fwd(const float* x, const float* w_packed, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W,
                         int32_t ksize, int32_t dilation, const mspl_epilogue_t* ep, float* out, void* stream);
 
+/* K13 in split-bf16 arithmetic: an opt-in matrix mode for the inference path of the ASPP heads (nn_layers/aspp.py:40-43,87-90).
+ * The convolution, shapes, x, out and epilogue restrictions of mspl_dense_conv_fwd; the products run on the bf16 matrix
+ * instruction with fp32 accumulation.
+ *   Split rule (weights and activations alike), planes = 2 or 3:  r_0 = v,  plane_i = bf16_rne(r_i),  r_{i+1} = r_i - float(plane_i)
+ *     (exact in fp32).  The kernel keeps the products plane_i(w) * plane_j(x) with i + j < planes: 3 for planes = 2 ("bf16x3"),
+ *     6 for planes = 3 ("bf16x6"); all of them add into the same fp32 accumulators.
+ *   Pack: w_split holds the weight already split, bf16 bit patterns laid out (planes, k*k, Cout, Cin), Cin contiguous, 16-byte
+ *     aligned (plane p is the bf16 plane of mspl_dense_conv_fwd's w_packed); activations are split inside the kernel.
+ *   Contract: inputs and weights finite and in the normal fp32 range.  Non-finite values (an infinity splits into an infinity and
+ *     a NaN) and magnitudes whose low planes would be bf16-subnormal are outside it.  The output is fp32.  The summation order is
+ *     fixed: the same inputs give the same bits, whatever the batch around an image.
+ * mspl_dense_conv_split_fits: 1 when the kernel takes (Cin, Cout, ksize, planes), else 0; never depends on N, H, W.
+ * MSPL_ERR_UNSUPPORTED, with nothing launched, for other plane counts, ksize outside {1, 3}, Cin % 32 != 0 or a misaligned pack:
+ * the caller then runs mspl_dense_conv_fwd. */
+int mspl_dense_conv_split_fits(int32_t Cin, int32_t Cout, int32_t ksize, int32_t planes);
+int mspl_dense_conv_split_fwd(const float* x, const uint16_t* w_split, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W,
+                              int32_t ksize, int32_t dilation, int32_t planes, const mspl_epilogue_t* ep, float* out, void* stream);
+
 /* K13 backward: what Conv2d autograd computes for the ASPP heads in train() (nn_layers/aspp.py:40-51 / :87-98).
  *
  * Weight gradient, in the packed (k*k, Cout, Cin) layout of w_packed (the inverse permute gives (Cout, Cin, k, k) as a view):

@@ -148,6 +148,8 @@ SIGNATURES = {
                              [ctypes.POINTER(ctypes.c_void_p)] * 2 + [ctypes.c_void_p],
     'mspl_dense_conv_fwd': [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _EP, c_f32p,
                             ctypes.c_void_p],
+    'mspl_dense_conv_split_fits': [c_i32] * 4,
+    'mspl_dense_conv_split_fwd': [c_f32p, ctypes.c_void_p] + [c_i32] * 8 + [_EP, c_f32p, ctypes.c_void_p],
     'mspl_dense_conv_wgrad_workspace_bytes': [c_i32] * 8,
     'mspl_dense_conv_wgrad': [c_f32p, c_f32p] + [c_i32] * 8 + [ctypes.c_void_p, c_i64, c_f32p, c_f32p, ctypes.c_void_p],
     'mspl_dense_conv_dgrad': [ctypes.POINTER(ctypes.c_void_p)] * 2 + [ctypes.POINTER(c_i32)] * 2 + [c_i32] * 7 + [c_f32p, ctypes.c_void_p],

@@ -12,6 +12,16 @@ on autograd nodes with HIP backward kernels.  eval() with gradients enabled (fro
 Inference: the five branches write straight into their channel slice of one (N,1280,H,W) buffer.
 Training: each branch keeps its raw convolution output z (what the BatchNorm backward needs); the four convolutions of the
 feature map are ONE autograd node (one data-gradient launch into one gx), torch.cat builds the concatenation.
+
+Matrix mode (inference path only; `head.matrix_mode`, or `set_matrix_mode(model, mode)` for every head of a module tree):
+    'fp32'    the default: exact fp32 on v_mfma_f32_32x32x2_f32, bit-identical to a head that never heard of the mode
+    'bf16x3'  the four convolutions of the feature map and conv_1x1_3 split every fp32 operand into 2 bf16 planes and keep the 3
+              products plane_i(w) * plane_j(x) with i + j < 2 on the bf16 matrix instruction, fp32 accumulation
+    'bf16x6'  3 planes, the 6 products with i + j < 3: indistinguishable from float64 arithmetic at fp32 output precision
+  Split rule: r_0 = v, plane_i = bf16_rne(r_i), r_{i+1} = r_i - float(plane_i).  Contract: inputs and weights finite and in the
+  normal fp32 range (an infinity splits into an infinity and a NaN; magnitudes whose low planes would be bf16-subnormal lose
+  them); the output is fp32; the summation order is fixed, so the same inputs give the same bits.  The pooled 1x1 (N pixels) and
+  the classifier stay fp32, and so does the whole training path: _forward_train ignores the mode.
 """
 import torch
 from torch import nn
@@ -21,7 +31,27 @@ from .layers import bn_fold, cached
 from .ops import Epi
 
 
+MATRIX_MODES = {'fp32': 0, 'bf16x3': 2, 'bf16x6': 3}        # mode -> bf16 planes per operand (0: no split)
+
+
+def _check_mode(mode):
+    if mode not in MATRIX_MODES:
+        raise ValueError('mspl_amd: matrix_mode %r (one of %s)' % (mode, ', '.join(repr(m) for m in MATRIX_MODES)))
+    return mode
+
+
+def set_matrix_mode(module, mode):
+    """Set `matrix_mode` on every ASPP head found in `module`'s tree (the module itself included); returns how many there were."""
+    _check_mode(mode)
+    heads = [m for m in module.modules() if isinstance(m, _ASPPBase)]
+    for m in heads:
+        m.matrix_mode = mode
+    return len(heads)
+
+
 class _ASPPBase(nn.Module):
+    _matrix_mode = 'fp32'
+
     def __init__(self, in_channels, num_classes):
         super().__init__()
         self.conv_1x1_1 = nn.Conv2d(in_channels, 256, kernel_size=1)
@@ -39,8 +69,25 @@ class _ASPPBase(nn.Module):
         self.bn_conv_1x1_3 = nn.BatchNorm2d(256)
         self.conv_1x1_4 = nn.Conv2d(256, num_classes, kernel_size=1)
 
+    @property
+    def matrix_mode(self):
+        return self._matrix_mode
+
+    @matrix_mode.setter
+    def matrix_mode(self, mode):
+        self._matrix_mode = _check_mode(mode)
+
     def _packed(self, conv):
         return cached(conv, 'packed', [conv.weight], lambda: ops.pack_dense_weight(conv.weight))
+
+    def _dense(self, x, conv, ep, out=None):
+        """One dense convolution of the inference path in this head's matrix mode (exact fp32 where the split kernel does not fit)."""
+        k, dil = conv.kernel_size[0], conv.dilation[0]
+        planes = MATRIX_MODES[self._matrix_mode]
+        if planes and ops.dense_conv_split_fits(conv.in_channels, conv.out_channels, k, planes):
+            ws = cached(conv, 'packed_split%d' % planes, [conv.weight], lambda: ops.pack_dense_weight_split(conv.weight, planes))
+            return ops.dense_conv_split(x, ws, k, dil, ep, out=out)
+        return ops.dense_conv(x, self._packed(conv), k, dil, ep, out=out)
 
     def _epi(self, conv, bn, ctot=None, coff=0):
         """relu(bn(conv(x) + bias)) as scale / shift / alpha = 0: shift = bn_shift + bias * bn_scale.  Epilogue vectors are
@@ -96,16 +143,14 @@ class _ASPPBase(nn.Module):
     def _forward_infer(self, feature_map):
         N, _, H, W = feature_map.shape
         cat = torch.empty((N, 1280, H, W), device=feature_map.device, dtype=torch.float32)
-        ops.dense_conv(feature_map, self._packed(self.conv_1x1_1), 1, 1, self._epi(self.conv_1x1_1, self.bn_conv_1x1_1, 1280, 0),
-                       out=(cat, 0))
+        self._dense(feature_map, self.conv_1x1_1, self._epi(self.conv_1x1_1, self.bn_conv_1x1_1, 1280, 0), out=(cat, 0))
         for i, (conv, bn) in enumerate([(self.conv_3x3_1, self.bn_conv_3x3_1), (self.conv_3x3_2, self.bn_conv_3x3_2),
                                         (self.conv_3x3_3, self.bn_conv_3x3_3)]):
-            ops.dense_conv(feature_map, self._packed(conv), 3, conv.dilation[0], self._epi(conv, bn, 1280, 256 * (i + 1)),
-                           out=(cat, 256 * (i + 1)))
+            self._dense(feature_map, conv, self._epi(conv, bn, 1280, 256 * (i + 1)), out=(cat, 256 * (i + 1)))
         img = ops.adaptive_avgpool(feature_map, (1, 1))
         img = ops.dense_conv(img, self._packed(self.conv_1x1_2), 1, 1, self._epi(self.conv_1x1_2, self.bn_conv_1x1_2))
         ops.bilinear(img, (H, W), out=(cat, 1024))            # bilinear from a 1x1 map: the constant, whatever align_corners is
-        out = ops.dense_conv(cat, self._packed(self.conv_1x1_3), 1, 1, self._epi(self.conv_1x1_3, self.bn_conv_1x1_3))
+        out = self._dense(cat, self.conv_1x1_3, self._epi(self.conv_1x1_3, self.bn_conv_1x1_3))
         c4 = self.conv_1x1_4
         return ops.conv1x1(out, c4.weight, 1, Epi(shift=c4.bias))
 

@@ -272,6 +272,46 @@ def dense_conv(x, w_packed, ksize, dilation=1, ep=None, out=None):
     return dst
 
 
+def pack_dense_weight_split(w, planes):
+    """(Cout, Cin, k, k) fp32 conv weight -> (planes, k*k, Cout, Cin) bfloat16: the weight split into bf16 planes by the rule of
+    mspl_dense_conv_split_fwd (plane_i = bf16_rne(r_i), r_{i+1} = r_i - float(plane_i), r_0 = w), each plane in the tap-major
+    layout of pack_dense_weight.  Plain torch ops: works on CPU tensors too."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 4 or w.shape[2] != w.shape[3] or w.dtype != torch.float32:
+        raise RuntimeError('mspl_amd: pack_dense_weight_split takes a float32 (Cout, Cin, k, k) weight')
+    if planes not in (2, 3):
+        raise RuntimeError('mspl_amd: pack_dense_weight_split: %r planes (2 or 3)' % (planes,))
+    Cout, Cin, k, _ = w.shape
+    r = w.detach().permute(2, 3, 0, 1).reshape(k * k, Cout, Cin)
+    out = torch.empty((planes, k * k, Cout, Cin), device=w.device, dtype=torch.bfloat16)
+    for p in range(planes):
+        out[p] = r.to(torch.bfloat16)              # round to nearest even
+        r = r - out[p].to(torch.float32)           # exact in fp32
+    return out
+
+
+def dense_conv_split_fits(Cin, Cout, ksize, planes):
+    """True when mspl_dense_conv_split_fwd takes this convolution (never depends on N, H, W)."""
+    return bool(lib.mspl_dense_conv_split_fits(int(Cin), int(Cout), int(ksize), int(planes)))
+
+
+def dense_conv_split(x, w_split, ksize, dilation=1, ep=None, out=None):
+    """K13 in split-bf16 arithmetic (the opt-in matrix mode of the ASPP heads): w_split from pack_dense_weight_split, whose plane
+    count (2: bf16x3, 3: bf16x6) selects the mode.  Shapes, epilogue and `out=(tensor, coff)` as dense_conv."""
+    x = _f32(x, 'x')
+    if not isinstance(w_split, torch.Tensor) or not w_split.is_cuda or w_split.dtype != torch.bfloat16 or not w_split.is_contiguous():
+        raise RuntimeError('mspl_amd: dense_conv_split weights must be a contiguous CUDA (ROCm) bfloat16 tensor from pack_dense_weight_split')
+    N, Cin, H, W = x.shape
+    taps = ksize * ksize
+    if w_split.dim() != 4 or w_split.shape[1] != taps or w_split.shape[3] != Cin:
+        raise RuntimeError('mspl_amd: dense_conv_split weight %s does not match k=%d Cin=%d' % (tuple(w_split.shape), ksize, Cin))
+    planes, Cout = w_split.shape[0], w_split.shape[2]
+    dst, coff = _dest(out, (N, Cout, H, W), x)
+    s, keep = _build(ep, dst, coff, N, Cout, H * W)
+    check(lib.mspl_dense_conv_split_fwd(_p(x), _p(w_split), N, Cin, Cout, H, W, ksize, int(dilation), planes, ctypes.byref(s), _p(dst),
+                                        _stream()))
+    return dst
+
+
 def pack_dense_weight_dgrad(w):
     """(Cout, Cin, k, k) conv weight -> the (k*k, Cin, Cout) weights of its data gradient as a dense_conv of gy (stride 1,
     padding = dilation): transposed and tap-reversed, Wt[t][ci][co] = Wp[k*k - 1 - t][co][ci] (a permute copy)."""
