@@ -377,6 +377,23 @@ int mspl_conv_bwd_data(const float* gy, const float* w, int32_t N, int32_t Cin, 
 int mspl_conv_bwd_weight(const float* gy, const float* x, int32_t N, int32_t Cin, int32_t Cout, int32_t groups,
                          int32_t H, int32_t W, int32_t K, int32_t stride, int32_t dilation, int32_t accumulate,
                          float* gw, void* stream);
+
+/* The kernel form mspl_conv_bwd_weight launches for a shape, one value per launch site. */
+typedef enum {
+    MSPL_WGRAD_1X1_MFMA = 1,        /* 1x1 on the matrix cores: cin_g, cout_g >= 8 and Ho*Wo % 4 == 0 */
+    MSPL_WGRAD_1X1_LDS = 2,         /* 1x1 with 16x16 LDS tiles */
+    MSPL_WGRAD_STEM_S2_STRIP = 3,   /* 3x3, cin_g == 3, stride 2: strips of four output pixels */
+    MSPL_WGRAD_STEM_COB4 = 4,       /* 3x3, cin_g == 3: four output channels per workgroup */
+    MSPL_WGRAD_STRIP = 5,           /* 3x3, cin_g in {1..5, 8}, stride 1, W % 4 == 0: strips */
+    MSPL_WGRAD_G3X3 = 6,            /* 3x3, cin_g in {1..5, 8}: one output pixel per thread */
+    MSPL_WGRAD_GENERIC = 7
+} mspl_wgrad_form_t;
+/* What the launcher above decides for a shape, from the same host function it calls itself (no device call, no state): *form (an
+ * mspl_wgrad_form_t) and *parts, the number of chunks the N*Ho*Wo reduction range is split into.  For MSPL_WGRAD_1X1_MFMA *parts is
+ * the number of waves that share one 32x32 tile and *ngroups (may be NULL; 0 for the other forms) the number of 64-pixel groups they
+ * stride over.  aligned16: whether gy and x are both 16-byte aligned, which the strip forms require. */
+int mspl_conv_bwd_weight_plan(int32_t N, int32_t Cin, int32_t Cout, int32_t groups, int32_t H, int32_t W, int32_t K, int32_t stride,
+                              int32_t dilation, int32_t aligned16, int32_t* form, int32_t* parts, int32_t* ngroups);
 /* Weight gradients of nprob grouped 1x1 convolutions in as few launches as possible, each ACCUMULATED (atomically) into gw[i] --
  *     parameter gradient buffers that were zeroed at the start of the step.  Problem i: gy[i] (N,Cout,HW), x[i] (N,Cin,HW),
  *     gw[i] (Cout, Cin/groups).  Nothing in a backward chain waits for a weight gradient, so the training steps queue them
@@ -730,6 +747,8 @@ int mspl_nid_hist_bwd(const float* camera, const float* label, int32_t B, int32_
  * the caller, or the parameters' own gradient buffers), NULL = skip. */
 int mspl_eesp_dw_bwd(const float* gs, const float* x, const float* w4, const int32_t* dil, int32_t stride, int32_t N,
                      int32_t n, int32_t H, int32_t W, float* gx, float* const* gw, void* stream);
+/* The number of chunks its weight-gradient launch splits the N*Ho*Wo output positions of a channel into (host only; 0: bad shape). */
+int mspl_eesp_dw_bwd_weight_chunks(int32_t N, int32_t n, int32_t H, int32_t W, int32_t stride);
 
 /* Stride-1 EESP block, everything between conv_1x1_exp's data gradient and proj_1x1's BatchNorm in ONE launch (nn_layers/eesp.py:68-80
  * backward): br_after_cat's BatchNorm + PReLU backward, the HFF suffix sum, the data gradient and the weight gradients of the four
@@ -738,8 +757,10 @@ int mspl_eesp_dw_bwd(const float* gs, const float* x, const float* w4, const int
  * gscale/gshift/galpha (4n) ACCUMULATED.  With proj_c (N,n,H,W) = proj_1x1's bare convolution result (x = PReLU(proj_c * proj_scale +
  * proj_shift)), proj_1x1's BatchNorm + PReLU backward is applied before the store: gx is then dL/d(proj_c) and g_proj_scale /
  * g_proj_shift / g_proj_alpha (n, ACCUMULATED; d gamma / d beta with proj_mean / proj_inv) its parameter gradients; proj_c NULL:
- * gx = dL/dx.  _fits: 1 when the haloed row band fits LDS. */
+ * gx = dL/dx.  _fits: 1 when the haloed row band fits LDS.  _bands: 0 where _fits is, else the number of row bands a plane is
+ * split into, with *band_rows (may be NULL) the rows of each but the last; both from the launcher's own plan (host only). */
 int mspl_eesp_bwd_fused_fits(int32_t N, int32_t n, int32_t H, int32_t W, const int32_t* dil);
+int mspl_eesp_bwd_fused_bands(int32_t N, int32_t n, int32_t H, int32_t W, const int32_t* dil, int32_t* band_rows);
 int mspl_eesp_bwd_fused(const float* z, const float* gy, const float* x, const float* w4, const int32_t* dil,
                         const float* scale, const float* shift, const float* alpha, const float* bn_mean,
                         const float* bn_inv, int32_t N, int32_t n, int32_t H, int32_t W, float* gx, float* const* gw,

@@ -44,6 +44,8 @@ FILTER_BILINEAR = 2             # MSPL_FILTER_BILINEAR
 
 ABI_VERSION = 4                 # include/mspl_hip.h: mspl_abi_version()
 ERR_UNSUPPORTED = -2            # MSPL_ERR_UNSUPPORTED
+# mspl_wgrad_form_t: what mspl_conv_bwd_weight_plan reports
+WGRAD_1X1_MFMA, WGRAD_1X1_LDS, WGRAD_STEM_S2_STRIP, WGRAD_STEM_COB4, WGRAD_STRIP, WGRAD_G3X3, WGRAD_GENERIC = range(1, 8)
 LAUNCH_THROUGHPUT = 1           # MSPL_LAUNCH_THROUGHPUT
 LAUNCH_K2_STREAM_OFF = 2        # MSPL_LAUNCH_K2_STREAM_OFF
 LAUNCH_K2_STREAM_FORCE = 4      # MSPL_LAUNCH_K2_STREAM_FORCE
@@ -101,6 +103,9 @@ SIGNATURES = {
     'mspl_label_epilogue_hist_fits': [c_i32] * 8,
     'mspl_conv_bwd_data': [c_f32p, c_f32p] + [c_i32] * 10 + [c_f32p, ctypes.c_void_p],
     'mspl_conv_bwd_weight': [c_f32p, c_f32p] + [c_i32] * 10 + [c_f32p, ctypes.c_void_p],
+    'mspl_conv_bwd_weight_plan': [c_i32] * 10 + [ctypes.POINTER(c_i32)] * 3,
+    'mspl_eesp_dw_bwd_weight_chunks': [c_i32] * 5,
+    'mspl_eesp_bwd_fused_bands': [c_i32] * 4 + [ctypes.POINTER(c_i32)] * 2,
     'mspl_affine_prelu_bwd': [c_f32p] * 7 + [c_i32] * 3 + [c_f32p] * 5 + [ctypes.c_void_p],
     'mspl_bn_train_small_fits': [c_i32] * 3,
     'mspl_bn_train_small_fwd': [c_f32p] * 5 + [c_i32] * 3 + [ctypes.c_float] * 2 + [c_f32p] * 2 + [ctypes.c_void_p] + [c_f32p] * 5 + [ctypes.c_void_p],

@@ -281,16 +281,15 @@ int conv1x1_wgrad_mfma_batch(const float* const* gy, const float* const* x, floa
     return n;
 }
 
-// Called by mspl_conv_bwd_weight for K == 1 (gw already zeroed unless accumulating).  Returns 1 when the shape is left to the
-// 16x16 LDS kernel (tiny groups such as the 3-channel image reinforcement, planes that are not a multiple of 4 pixels).
-int conv1x1_wgrad_mfma_try(const float* gy, const float* x, int N, int G, int M, int K, int P, float* gw, hipStream_t s) {
-    if (M < 8 || K < 8 || (P & 3) != 0) return 1;
-    WgG g;
+// The single-problem geometry (host only): false when the shape is left to the 16x16 LDS kernel (tiny groups such as the 3-channel
+// image reinforcement, planes that are not a multiple of 4 pixels).
+static bool wgrad_try_geom(int N, int G, int M, int K, int P, WgG& g, int64_t& blocks) {
+    if (M < 8 || K < 8 || (P & 3) != 0) return false;
     g.N = N; g.G = G; g.M = M; g.K = K; g.P = P;
     g.tm = ceil_div(M, 32); g.tk = ceil_div(K, 32);
     const int64_t tiles = (int64_t)G * g.tm * g.tk;
     g.gpi = ceil_div(P, 64);
-    if ((int64_t)N * g.gpi >= (1ll << 30)) return 1;
+    if ((int64_t)N * g.gpi >= (1ll << 30)) return false;
     g.ngroups = N * g.gpi;
     // waves per tile: enough to put ~3 waves on every SIMD (MSPL_WGRAD_WAVES, 3072), at least MSPL_WGRAD_MINREP pixel groups per
     // wave when the range allows (each workgroup leaves with 1024 atomics), never more waves than groups
@@ -301,8 +300,27 @@ int conv1x1_wgrad_mfma_try(const float* gy, const float* x, int N, int G, int M,
     if (ns < 4) ns = 4;
     if (ns > g.ngroups) ns = g.ngroups;
     g.nslots = (int)((ns + 3) & ~3ll);
-    const int64_t blocks = tiles * (g.nslots >> 2);
-    if (blocks >= (1ll << 31)) return 1;
+    blocks = tiles * (g.nslots >> 2);
+    return blocks < (1ll << 31);
+}
+
+// What conv1x1_wgrad_mfma_try would do with this shape, without doing it (mspl_conv_bwd_weight_plan): 0 and the waves per tile /
+// 64-pixel groups of the reduction range when the matrix-core kernel takes it, else 1.
+int conv1x1_wgrad_mfma_plan(int N, int G, int M, int K, int P, int* nslots, int* ngroups) {
+    WgG g;
+    int64_t blocks;
+    if (!wgrad_try_geom(N, G, M, K, P, g, blocks)) return 1;
+    *nslots = g.nslots;
+    *ngroups = g.ngroups;
+    return 0;
+}
+
+// Called by mspl_conv_bwd_weight for K == 1 (gw already zeroed unless accumulating).  Returns 1 when the shape is left to the
+// 16x16 LDS kernel.
+int conv1x1_wgrad_mfma_try(const float* gy, const float* x, int N, int G, int M, int K, int P, float* gw, hipStream_t s) {
+    WgG g;
+    int64_t blocks;
+    if (!wgrad_try_geom(N, G, M, K, P, g, blocks)) return 1;
     static const int lds_on = MSPL_TUNE_INT("MSPL_WGRAD_GLDS", 1);
     if (lds_on) hipLaunchKernelGGL(conv1x1_wgrad_mfma_lds_kernel, dim3((unsigned)blocks), dim3(256), 0, s, gy, x, g, gw);
     else hipLaunchKernelGGL(conv1x1_wgrad_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, s, gy, x, g, gw);

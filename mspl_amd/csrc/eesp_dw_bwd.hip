@@ -172,6 +172,19 @@ __global__ __launch_bounds__(256) void eesp_dw_bwd_weight_kernel(const float* __
 
 using namespace mspl;
 
+// Chunks of the N*Ho*Wo output positions one channel's weight gradient is split into (eesp_dw_bwd_weight_kernel).
+static int dw_bwd_weight_chunks(int N, int n, int Ho, int Wo) {
+    const int64_t total = (int64_t)N * Ho * Wo;
+    int chunks = 1;
+    while ((int64_t)n * chunks < 2048 && total / (chunks * 2) >= 1024) chunks *= 2;
+    return chunks;
+}
+
+extern "C" int mspl_eesp_dw_bwd_weight_chunks(int32_t N, int32_t n, int32_t H, int32_t W, int32_t stride) {
+    if (N <= 0 || n <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
+    return dw_bwd_weight_chunks(N, n, (H - 1) / stride + 1, (W - 1) / stride + 1);
+}
+
 // gs: suffix-summed output gradient, branch-major (4,N,n,Ho,Wo) (mspl_hff_suffix_sum); x: (N,n,H,W); w4: (4,n,3,3).
 // gx (N,n,H,W) is overwritten (NULL: skipped).  gw[k] (n,3,3) each: ACCUMULATED into (caller zeroes, or passes the parameters'
 // gradient buffers); gw == NULL skips the weight gradient.
@@ -204,9 +217,7 @@ extern "C" int mspl_eesp_dw_bwd(const float* gs, const float* x, const float* w4
             MSPL_REQUIRE(gw[k], MSPL_ERR_NULL_POINTER, "eesp_dw_bwd: gw[%d] is NULL", k);
             ptrs.p[k] = gw[k];
         }
-        const int64_t total = (int64_t)N * g.Ho * g.Wo;
-        int chunks = 1;
-        while ((int64_t)n * chunks < 2048 && total / (chunks * 2) >= 1024) chunks *= 2;
+        const int chunks = dw_bwd_weight_chunks(N, n, g.Ho, g.Wo);
         hipLaunchKernelGGL(eesp_dw_bwd_weight_kernel, dim3((unsigned)(n * chunks)), dim3(256), 0, s, gs, x, g, chunks, ptrs);
         MSPL_CHECK_LAUNCH("eesp_dw_bwd(weight)");
     }
@@ -444,6 +455,13 @@ static size_t fb_plan(int N, int n, int H, int W, const int32_t* dil, FbGeom& g)
 extern "C" int mspl_eesp_bwd_fused_fits(int32_t N, int32_t n, int32_t H, int32_t W, const int32_t* dil) {
     FbGeom g;
     return fb_plan(N, n, H, W, dil, g) > 0 && (int64_t)N * n * g.bands < (1ll << 31);
+}
+
+extern "C" int mspl_eesp_bwd_fused_bands(int32_t N, int32_t n, int32_t H, int32_t W, const int32_t* dil, int32_t* band_rows) {
+    FbGeom g;
+    if (!(fb_plan(N, n, H, W, dil, g) > 0 && (int64_t)N * n * g.bands < (1ll << 31))) return 0;
+    if (band_rows) *band_rows = g.BH;
+    return g.bands;
 }
 
 static int eesp_bwd_fused_launch(const float* z, const float* gy, const float* x, const float* w4, const int32_t* dil,

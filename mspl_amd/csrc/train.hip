@@ -14,6 +14,7 @@
 namespace mspl {
 
 int conv1x1_wgrad_mfma_try(const float* gy, const float* x, int N, int G, int M, int K, int P, float* gw, hipStream_t s);
+int conv1x1_wgrad_mfma_plan(int N, int G, int M, int K, int P, int* nslots, int* ngroups);
 int conv1x1_wgrad_mfma_batch(const float* const* gy, const float* const* x, float* const* gw, const float* const* rowscale, const int* N,
                              const int* G, const int* M, const int* K, const int* P, int nprob, hipStream_t s);
 
@@ -1202,6 +1203,74 @@ extern "C" int mspl_conv1x1_wgrad_batch(const float* const* gy, const float* con
     return MSPL_OK;
 }
 
+// Which kernel form mspl_conv_bwd_weight launches for a shape and into how many parts it splits the reduction: the ONE place where
+// that is decided (the launcher below switches on the result; mspl_conv_bwd_weight_plan hands it to callers and tests).
+// aligned16: gy and x are both 16-byte aligned (the strip forms read them as float4).
+struct WgradPlan {
+    int form;            // mspl_wgrad_form_t
+    int parts;           // chunks of the N*Ho*Wo range (matrix-core 1x1: waves per tile)
+    int ngroups;         // matrix-core 1x1: 64-pixel groups of the reduction range; else 0
+};
+
+static WgradPlan conv_bwd_weight_plan(const ConvGeom& g, bool aligned16) {
+    WgradPlan p;
+    p.ngroups = 0;
+    const int K = g.K, Cout = g.Cout;
+    const int64_t total = (int64_t)g.N * g.Ho * g.Wo;
+    static const int s2_strip = MSPL_TUNE_INT("MSPL_G3X3_WGRAD_S2STRIP", 1);
+    static const int strip_form = MSPL_TUNE_INT("MSPL_G3X3_WGRAD_STRIP", 1);
+    int chunks = 1;
+    if (K == 1) {
+        static const bool no_mfma = MSPL_TUNE_INT("MSPL_WGRAD_LDS", 0) != 0;      // A/B aid: force the 16x16 LDS kernel
+        if (!no_mfma && conv1x1_wgrad_mfma_plan(g.N, g.G, g.cout_g, g.cin_g, g.Ho * g.Wo, &p.parts, &p.ngroups) == 0) {
+            p.form = MSPL_WGRAD_1X1_MFMA;
+            return p;
+        }
+        p.ngroups = 0;
+        // (the 16x16 tile is zero padded for groups with fewer channels, e.g. the 3-channel image reinforcement)
+        const int tiles_m = ceil_div(g.cout_g, 16), tiles_k = ceil_div(g.cin_g, 16);
+        const int64_t base = (int64_t)g.G * tiles_m * tiles_k;
+        static const int minpx = MSPL_TUNE_INT("MSPL_WGRAD16_MINPX", 256);
+        while (base * chunks < 2048 && total / (chunks * 2) >= minpx) chunks *= 2;
+        p.form = MSPL_WGRAD_1X1_LDS;
+    } else if (s2_strip && K == 3 && g.cin_g == 3 && g.cout_g % 4 == 0 && Cout >= 16 && g.stride == 2 && g.dil == 1 && g.pad == 1 &&
+               (g.W & 7) == 0 && (g.H & 1) == 0 && aligned16) {
+        const int64_t strips = total / 4;
+        while ((int64_t)(Cout / 2) * chunks < 2048 && strips / (chunks * 2) >= 512) chunks *= 2;
+        p.form = MSPL_WGRAD_STEM_S2_STRIP;
+    } else if (K == 3 && g.cin_g == 3 && g.cout_g % 4 == 0 && Cout >= 16) {       // the stem: four output channels per workgroup share the taps
+        while ((int64_t)(Cout / 4) * chunks < 2048 && total / (chunks * 2) >= 2048) chunks *= 2;
+        p.form = MSPL_WGRAD_STEM_COB4;
+    } else if (strip_form && K == 3 && (g.cin_g <= 5 || g.cin_g == 8) && g.stride == 1 && g.dil == 1 && g.pad == 1 && (g.W & 3) == 0 &&
+               aligned16) {
+        const int64_t strips = total / 4;
+        while ((int64_t)Cout * chunks < 2048 && strips / (chunks * 2) >= 1024) chunks *= 2;
+        p.form = MSPL_WGRAD_STRIP;
+    } else if (K == 3 && (g.cin_g <= 5 || g.cin_g == 8)) {
+        while ((int64_t)Cout * chunks < 4096 && total / (chunks * 2) >= 2048) chunks *= 2;
+        p.form = MSPL_WGRAD_G3X3;
+    } else {
+        const int64_t nw = (int64_t)Cout * g.cin_g * K * K;
+        while (nw * chunks < 2048 && total / (chunks * 2) >= 4096) chunks *= 2;
+        p.form = MSPL_WGRAD_GENERIC;
+    }
+    p.parts = chunks;
+    return p;
+}
+
+extern "C" int mspl_conv_bwd_weight_plan(int32_t N, int32_t Cin, int32_t Cout, int32_t groups, int32_t H, int32_t W, int32_t K,
+                                         int32_t stride, int32_t dilation, int32_t aligned16, int32_t* form, int32_t* parts,
+                                         int32_t* ngroups) {
+    MSPL_REQUIRE(form && parts, MSPL_ERR_NULL_POINTER, "conv_bwd_weight_plan: null pointer");
+    ConvGeom g;
+    if (int rc = conv_geom("conv_bwd_weight_plan", N, Cin, Cout, groups, H, W, K, stride, dilation, g)) return rc;
+    const WgradPlan p = conv_bwd_weight_plan(g, aligned16 != 0);
+    *form = p.form;
+    *parts = p.parts;
+    if (ngroups) *ngroups = p.ngroups;
+    return MSPL_OK;
+}
+
 extern "C" int mspl_conv_bwd_weight(const float* gy, const float* x, int32_t N, int32_t Cin, int32_t Cout, int32_t groups,
                                     int32_t H, int32_t W, int32_t K, int32_t stride, int32_t dilation, int32_t accumulate,
                                     float* gw, void* stream) {
@@ -1214,49 +1283,34 @@ extern "C" int mspl_conv_bwd_weight(const float* gy, const float* x, int32_t N, 
         hipError_t e = hipMemsetAsync(gw, 0, (size_t)nw * sizeof(float), s);      // async memset node: graph-capturable
         MSPL_REQUIRE(e == hipSuccess, MSPL_ERR_HIP, "conv_bwd_weight: memset failed: %s", hipGetErrorString(e));
     }
-    const int64_t total = (int64_t)N * g.Ho * g.Wo;
-    if (K == 1) {
-        static const bool no_mfma = MSPL_TUNE_INT("MSPL_WGRAD_LDS", 0) != 0;      // A/B aid: force the 16x16 LDS kernel
-        if (!no_mfma && conv1x1_wgrad_mfma_try(gy, x, N, groups, g.cout_g, g.cin_g, g.Ho * g.Wo, gw, s) == 0) {
-            MSPL_CHECK_LAUNCH("conv_bwd_weight(1x1, mfma)");
-            return MSPL_OK;
-        }
-        // (the 16x16 tile is zero padded for groups with fewer channels, e.g. the 3-channel image reinforcement)
+    const WgradPlan plan = conv_bwd_weight_plan(g, ((((uintptr_t)gy) | ((uintptr_t)x)) & 15) == 0);
+    const int chunks = plan.parts;
+    switch (plan.form) {
+    case MSPL_WGRAD_1X1_MFMA: {
+        const int rc = conv1x1_wgrad_mfma_try(gy, x, N, groups, g.cout_g, g.cin_g, g.Ho * g.Wo, gw, s);
+        MSPL_REQUIRE(rc == 0, MSPL_ERR_UNSUPPORTED, "conv_bwd_weight: the matrix-core 1x1 form refused a shape its plan accepted");
+        MSPL_CHECK_LAUNCH("conv_bwd_weight(1x1, mfma)");
+        return MSPL_OK;
+    }
+    case MSPL_WGRAD_1X1_LDS: {
         const int tiles_m = ceil_div(g.cout_g, 16), tiles_k = ceil_div(g.cin_g, 16);
-        int64_t base = (int64_t)groups * tiles_m * tiles_k;
-        int chunks = 1;
-        static const int minpx = MSPL_TUNE_INT("MSPL_WGRAD16_MINPX", 256);
-        while (base * chunks < 2048 && total / (chunks * 2) >= minpx) chunks *= 2;
-        const int64_t blocks = base * chunks;
+        const int64_t blocks = (int64_t)groups * tiles_m * tiles_k * chunks;
         MSPL_REQUIRE(blocks < (1ll << 31), MSPL_ERR_BAD_SHAPE, "conv_bwd_weight: grid too large");
         hipLaunchKernelGGL(conv1x1_bwd_weight_kernel, dim3((unsigned)blocks), dim3(256), 0, s, gy, x, g, chunks, tiles_m, tiles_k, gw);
         MSPL_CHECK_LAUNCH("conv_bwd_weight(1x1)");
         return MSPL_OK;
     }
-    static const int s2_strip = MSPL_TUNE_INT("MSPL_G3X3_WGRAD_S2STRIP", 1);
-    if (s2_strip && K == 3 && g.cin_g == 3 && g.cout_g % 4 == 0 && Cout >= 16 && g.stride == 2 && g.dil == 1 && g.pad == 1 && (g.W & 7) == 0 &&
-        (g.H & 1) == 0 && ((((uintptr_t)gy) | ((uintptr_t)x)) & 15) == 0) {
-        const int64_t strips = total / 4;
-        int chunks = 1;
-        while ((int64_t)(Cout / 2) * chunks < 2048 && strips / (chunks * 2) >= 512) chunks *= 2;
+    case MSPL_WGRAD_STEM_S2_STRIP: {
         const int64_t pairs8 = ((int64_t)g.G * chunks + 7) & ~7ll;
         hipLaunchKernelGGL((g3x3_bwd_weight_s2_strip_kernel<3, 2>), dim3((unsigned)(pairs8 * (g.cout_g / 2))), dim3(256), 0, s, gy, x, g, chunks, gw);
         MSPL_CHECK_LAUNCH("conv_bwd_weight(3x3 stride 2, few input channels, strips)");
         return MSPL_OK;
     }
-    if (K == 3 && g.cin_g == 3 && g.cout_g % 4 == 0 && Cout >= 16) {       // the stem: four output channels per workgroup share the taps
-        int chunks = 1;
-        while ((int64_t)(Cout / 4) * chunks < 2048 && total / (chunks * 2) >= 2048) chunks *= 2;
+    case MSPL_WGRAD_STEM_COB4:
         hipLaunchKernelGGL((g3x3_bwd_weight_cob_kernel<3, 4>), dim3((unsigned)(Cout / 4 * chunks)), dim3(256), 0, s, gy, x, g, chunks, gw);
         MSPL_CHECK_LAUNCH("conv_bwd_weight(3x3, few input channels, 4 output channels per workgroup)");
         return MSPL_OK;
-    }
-    static const int strip_form = MSPL_TUNE_INT("MSPL_G3X3_WGRAD_STRIP", 1);
-    if (strip_form && K == 3 && (g.cin_g <= 5 || g.cin_g == 8) && g.stride == 1 && g.dil == 1 && g.pad == 1 && (g.W & 3) == 0 &&
-        ((((uintptr_t)gy) | ((uintptr_t)x)) & 15) == 0) {
-        const int64_t strips = total / 4;
-        int chunks = 1;
-        while ((int64_t)Cout * chunks < 2048 && strips / (chunks * 2) >= 1024) chunks *= 2;
+    case MSPL_WGRAD_STRIP: {
         const int64_t pairs8 = ((int64_t)g.G * chunks + 7) & ~7ll;                 // (group, chunk) pairs, padded to whole rounds of the 8 XCDs
         const dim3 grid((unsigned)(pairs8 * g.cout_g)), blk(256);
         switch (g.cin_g) {
@@ -1270,9 +1324,7 @@ extern "C" int mspl_conv_bwd_weight(const float* gy, const float* x, int32_t N, 
         MSPL_CHECK_LAUNCH("conv_bwd_weight(3x3, few input channels, strips)");
         return MSPL_OK;
     }
-    if (K == 3 && (g.cin_g <= 5 || g.cin_g == 8)) {
-        int chunks = 1;
-        while ((int64_t)Cout * chunks < 4096 && total / (chunks * 2) >= 2048) chunks *= 2;
+    case MSPL_WGRAD_G3X3: {
         const dim3 grid((unsigned)(Cout * chunks)), blk(256);
         switch (g.cin_g) {
             case 1: hipLaunchKernelGGL(g3x3_bwd_weight_kernel<1>, grid, blk, 0, s, gy, x, g, chunks, gw); break;
@@ -1285,8 +1337,8 @@ extern "C" int mspl_conv_bwd_weight(const float* gy, const float* x, int32_t N, 
         MSPL_CHECK_LAUNCH("conv_bwd_weight(3x3, few input channels)");
         return MSPL_OK;
     }
-    int chunks = 1;
-    while (nw * chunks < 2048 && total / (chunks * 2) >= 4096) chunks *= 2;
+    default: break;
+    }
     const int64_t blocks = nw * chunks;
     MSPL_REQUIRE(blocks < (1ll << 31), MSPL_ERR_BAD_SHAPE, "conv_bwd_weight: grid too large");
     hipLaunchKernelGGL(conv_bwd_weight_kernel, dim3((unsigned)blocks), dim3(256), 0, s, gy, x, g, chunks, gw);
