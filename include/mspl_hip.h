@@ -352,6 +352,27 @@ int mspl_label_epilogue_hist_fwd(const float* main, const float* aux, int32_t N,
                                  const uint8_t* lut, uint8_t* labels, float* kld, unsigned long long* hist,
                                  int32_t num_classes, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* K8+K9 from the heads' PLANES: the final 1x1 classifier of both decoder heads (EfficientPyrPool with last_layer_br=False:
+ *     nn_layers/efficient_pyramid_pool.py:29,58 -- merge_layer's last convolution with its bias, nothing behind it;
+ *     model/segmentation/espdnet_ue.py:299-302) is computed inside the label epilogue, whose staging forms the C logits of the
+ *     source positions a tile needs instead of reading them: the (N,C,h,w) logits of the two heads are never written.  Then
+ *     exactly mspl_label_epilogue_hist_fwd (uest_seg_multi_os.py:685-691, :785-815, :903-912).
+ *     main_planes: (N,P,Hm,Wm); main_w: (C,P) as the convolution keeps it; main_b: (C).  aux_*: the second head with (Ha,Wa), or
+ *     aux_planes NULL (single-head nets).  Logit c of a position = bias[c] + sum_k w[c][k] * plane_k, k ascending in fused
+ *     multiply-adds: the summation order of mspl_conv1x1_fwd at these shapes, so labels / kld / hist are those of
+ *     mspl_conv1x1_fwd followed by mspl_label_epilogue_hist_fwd, bit for bit.
+ *     labels required; kld, lut optional; hist optional (NULL: labels only -- workspace is then unused), else num_classes and
+ *     the workspace contract of mspl_label_epilogue_hist_fwd.  No allocation, no synchronisation: capturable into a graph.
+ * _fits: 1 when the shape is covered: what mspl_label_epilogue_hist_fits accepts, with P in {4, 8, 12, 16}; the caller runs the
+ *     classifier and the logits entry otherwise (_fwd returns MSPL_ERR_UNSUPPORTED). */
+int mspl_label_epilogue_planes_fits(int32_t N, int32_t P, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa,
+                                    int32_t H, int32_t W);
+int mspl_label_epilogue_planes_fwd(const float* main_planes, const float* main_w, const float* main_b,
+                                   const float* aux_planes, const float* aux_w, const float* aux_b, int32_t N, int32_t P,
+                                   int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
+                                   const uint8_t* lut, uint8_t* labels, float* kld, unsigned long long* hist,
+                                   int32_t num_classes, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* K10  cross-source label merge + class histogram.  Replaces uest_seg_multi_os.py:695-718
  *     (merge_outputs) and :919-921.  src[s]: npix uint8 class maps (already in target ids),
  *     S <= 8, num_classes <= 32.  out[p] = first-max argmax_c count_c(p), or `fill` when the

@@ -101,6 +101,9 @@ SIGNATURES = {
                                      ctypes.c_void_p],
     'mspl_label_epilogue_hist_workspace_bytes': [c_i32, c_i32, c_i32],
     'mspl_label_epilogue_hist_fits': [c_i32] * 8,
+    'mspl_label_epilogue_planes_fits': [c_i32] * 9,
+    'mspl_label_epilogue_planes_fwd': [c_f32p] * 6 + [c_i32] * 9 + [ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_void_p, c_i32,
+                                       ctypes.c_void_p, c_i64, ctypes.c_void_p],
     'mspl_conv_bwd_data': [c_f32p, c_f32p] + [c_i32] * 10 + [c_f32p, ctypes.c_void_p],
     'mspl_conv_bwd_weight': [c_f32p, c_f32p] + [c_i32] * 10 + [c_f32p, ctypes.c_void_p],
     'mspl_conv_bwd_weight_plan': [c_i32] * 10 + [ctypes.POINTER(c_i32)] * 3,

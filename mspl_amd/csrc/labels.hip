@@ -216,14 +216,105 @@ struct LeStage {
     unsigned magqm, magqa; // exact divisions by wms / 4 and was / 4: (k * mag) >> 20 (verified on the host)
 };
 
+// Planes form of the staging (PLANES): the two heads arrive as the P planes in front of their final 1x1 classifier
+// (EfficientPyrPool's merge_layer[3], nn_layers/efficient_pyramid_pool.py:29,58 with last_layer_br=False) and the C logits of
+// every staged source position are formed here instead of being written and read back by a launch of their own.
+struct LePlanes {
+    const float* wm;  const float* bm;     // main head: weights (C, P) as the convolution keeps them, bias (C)
+    const float* wa;  const float* ba;     // aux head
+    int P;                                 // planes per head (<= 16, a multiple of 4); 0: the heads are logits
+};
+
+// Weights and bias are read through the constant address space: they do not change while the kernel runs and their addresses are
+// wave-uniform, so every read is a scalar load whatever the control flow around it looks like.
+typedef const __attribute__((address_space(4))) float* LeUniform;
+
+// One head's staging in the planes form.  A work item is (source row, 4-column chunk): its P plane values are requested
+// together (P 16-byte loads in flight per lane, or 4-byte loads where the rows are not 16-byte aligned), then the C logits of
+// the four columns are formed and written to the LDS slots the logits form fills: [row][class][column].  Weights and bias are
+// wave-uniform (one head per call): scalar loads, no per-lane weight traffic.  Summation order per logit: k ascending from
+// zero, fmaf(w[c][k], x[k], acc), then the bias through fmaf(acc, 1, b) -- conv1x1_thin_kernel with epi_apply's shift, which is
+// also the order of conv1x1_valu_kernel and of the k-ordered fp32 MFMA chain of conv1x1_pipe_kernel.
+// PC = 16 (the path's heads): classes unrolled, a class's 16 weights are one scalar load, requested a class ahead.
+// PC = 0: the plane count is `P` (4 / 8 / 12): one class at a time, four weights per scalar load.
+template <int CMAX, bool EXACT, int PC>
+__device__ __forceinline__ void le_stage_planes(const float* __restrict__ planes, const float* __restrict__ w,
+                                                const float* __restrict__ b, int P, int C, int plane, int rowlen, int r_lo,
+                                                int nrow, int cA, int c_hi, int vec, float* __restrict__ lds, int wst, int t) {
+    const int nq = ((c_hi - cA) >> 2) + 1;                       // chunks per staged row
+    for (int it = t; it < nrow * nq; it += 256) {
+        const int row = it / nq, q = it - row * nq;
+        const int col = cA + 4 * q;
+        const float* src = planes + (size_t)(r_lo + row) * rowlen + col;
+        float x[16][4];
+        if (vec) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (k < (PC ? PC : P)) v = *reinterpret_cast<const float4*>(src + (size_t)k * plane);
+                x[k][0] = v.x; x[k][1] = v.y; x[k][2] = v.z; x[k][3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[k][j] = (k < (PC ? PC : P) && col + j <= c_hi) ? src[(size_t)k * plane + j] : 0.f;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // (the weights do not depend on the item, and hoisted out of this loop -- which runs once or twice -- all C * P of them
+        // would have to live in scalar registers at once: keep their reads inside it)
+        asm volatile("" : "+s"(w), "+s"(b));
+        float* dst = lds + (size_t)row * C * wst + 4 * q;
+        if constexpr (PC == 16) {
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) {
+                if (EXACT || c < C) {
+                    const LeUniform wc = (LeUniform)(w + c * 16);
+                    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const float wk = wc[k];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[j] = fmaf(wk, x[k][j], acc[j]);
+                    }
+                    const float bc = ((LeUniform)b)[c];
+                    *reinterpret_cast<float4*>(dst + c * wst) =
+                        make_float4(fmaf(acc[0], 1.0f, bc), fmaf(acc[1], 1.0f, bc), fmaf(acc[2], 1.0f, bc), fmaf(acc[3], 1.0f, bc));
+                }
+            }
+        } else {
+#pragma unroll 1
+            for (int c = 0; c < C; ++c) {
+                const LeUniform wc = (LeUniform)(w + c * P);
+                float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int k0 = 0; k0 < 12; k0 += 4) {
+                    if (k0 < P) {                                   // uniform
+#pragma unroll
+                        for (int k = k0; k < k0 + 4; ++k) {
+                            const float wk = wc[k];
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) acc[j] = fmaf(wk, x[k][j], acc[j]);
+                        }
+                    }
+                }
+                const float bc = ((LeUniform)b)[c];
+                *reinterpret_cast<float4*>(dst + c * wst) =
+                    make_float4(fmaf(acc[0], 1.0f, bc), fmaf(acc[1], 1.0f, bc), fmaf(acc[2], 1.0f, bc), fmaf(acc[3], 1.0f, bc));
+            }
+        }
+    }
+}
+
 // EXACT: the class count equals CMAX (5 / 13 / 20, the path's heads): the per-class predicates `c < C` fold away (they were two
 // thirds of this kernel's 950 vector instructions per pixel).
 // WMS / WAS > 0: the staged row strides are these compile-time constants (480-pixel-wide outputs: 132 / 68), so the per-class LDS
 // offsets c * stride become immediate offsets of the ds_read instructions instead of one v_add_u32 per read (100 of the 590
 // vector instructions per pixel).
-template <int CMAX, bool EXACT, int WMS, int WAS>
+// PLANES: mainp / auxp are the heads' planes (N, P, Hm, Wm) / (N, P, Ha, Wa) and the staging forms the logits (le_stage_planes).
+template <int CMAX, bool EXACT, int WMS, int WAS, bool PLANES>
 __global__ __launch_bounds__(256) void label_epilogue_lds_kernel(const float* __restrict__ mainp, const float* __restrict__ auxp,
-                                                                 LeGeom g, LeStage st, const uint8_t* __restrict__ lut,
+                                                                 LeGeom g, LeStage st, LePlanes lp, const uint8_t* __restrict__ lut,
                                                                  uint8_t* __restrict__ labels, float* __restrict__ kld,
                                                                  unsigned int* __restrict__ hist_ws) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -260,7 +351,24 @@ __global__ __launch_bounds__(256) void label_epilogue_lds_kernel(const float* __
 
     // ---- stage.  Column j of a staged row <-> source column cmA + j, cmA = cm_lo rounded down to a multiple of 4.
     const int cmA = st.vec ? (cm_lo & ~3) : cm_lo, caA = st.vec ? (ca_lo & ~3) : ca_lo;
-    {
+    if constexpr (PLANES) {
+        // the main head's items go to the threads from the front, the aux head's from the back: at the path's shapes (33 x 3..4
+        // and 17 x 2..3 items) no wave takes both heads
+#pragma unroll 1
+        for (int head = 0; head < (auxp ? 2 : 1); ++head) {          // (one copy of the code: every choice below is uniform)
+            const bool ism = head == 0;
+            const int plane = ism ? g.Hm * g.Wm : g.Ha * g.Wa, rowlen = ism ? g.Wm : g.Wa;
+            const float* pb = (ism ? mainp : auxp) + (size_t)n * lp.P * plane;
+            const float* w = ism ? lp.wm : lp.wa;
+            const float* b = ism ? lp.bm : lp.ba;
+            const int r_lo = ism ? rm_lo : ra_lo, nrow = (ism ? rm_hi : ra_hi) - r_lo + 1;
+            const int cA = ism ? cmA : caA, c_hi = ism ? cm_hi : ca_hi, wst = ism ? st.wms : st.was;
+            float* lds = ism ? ml : al;
+            const int t = ism ? tid : 255 - tid;
+            if (lp.P == 16) le_stage_planes<CMAX, EXACT, 16>(pb, w, b, 16, g.C, plane, rowlen, r_lo, nrow, cA, c_hi, st.vec, lds, wst, t);
+            else le_stage_planes<CMAX, EXACT, 0>(pb, w, b, lp.P, g.C, plane, rowlen, r_lo, nrow, cA, c_hi, st.vec, lds, wst, t);
+        }
+    } else {
         const int mplane = g.Hm * g.Wm, aplane = g.Ha * g.Wa;
         const float* mb = mainp + (size_t)n * g.C * mplane;
         const float* ab = auxp ? auxp + (size_t)n * g.C * aplane : nullptr;
@@ -653,7 +761,8 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
                                int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
                                const uint8_t* lut, uint8_t* labels, float* prob, float* kld,
                                float* main_up, float* aux_up, unsigned long long* hist, int32_t ncls, void* workspace,
-                               int64_t workspace_bytes, void* stream) {
+                               int64_t workspace_bytes, void* stream, const LePlanes* planes = nullptr) {
+    // planes: mainp / aux are the heads' planes in front of their classifier (LePlanes; LDS-staged label form only)
     MSPL_REQUIRE(mainp, MSPL_ERR_NULL_POINTER, "label_epilogue: null main logits");
     MSPL_REQUIRE(labels || prob || kld || main_up || aux_up, MSPL_ERR_NULL_POINTER, "label_epilogue: no output requested");
     MSPL_REQUIRE(N > 0 && C > 0 && Hm > 0 && Wm > 0 && H > 0 && W > 0 && (!aux || (Ha > 0 && Wa > 0)),
@@ -669,6 +778,9 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
     hipStream_t st_ = (hipStream_t)stream;
     const bool label_form = !prob && !main_up && !aux_up && C <= 24 && H <= 65535 * LE_RB / 4 && N <= 65535 &&
                             (int64_t)N * C * Hm * Wm < (1ll << 31) && (int64_t)N * C * (int64_t)Ha * Wa < (1ll << 31);
+    LePlanes lp;
+    memset(&lp, 0, sizeof(lp));
+    if (planes) lp = *planes;
     if (label_form) {
         // LDS-staged form when the tile's source rows fit (they do for the x2 / x4 heads of the path); else the register form
         LeStage st;
@@ -688,7 +800,7 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
         }
         const size_t lds = ((size_t)st.nrm * C * st.wms + (size_t)st.nra * C * st.was + 32) * sizeof(float);
         static const int dbg_reg = MSPL_TUNE_INT("MSPL_LE_REG", 0);     // tuning aid: force the register form
-        if (lds <= 128 * 1024 && (st.nrm + st.nra) * C < 4096 && st.wms <= 256 && st.was <= 256 && (!st.vec || (st.wms <= 256 && st.was <= 256)) && !(dbg_reg && !hist)) {
+        if (lds <= 128 * 1024 && (st.nrm + st.nra) * C < 4096 && st.wms <= 256 && st.was <= 256 && (!st.vec || (st.wms <= 256 && st.was <= 256)) && !(dbg_reg && !hist && !planes)) {
             const dim3 grid((unsigned)ceil_div(W, 256), (unsigned)(4 * ceil_div(ceil_div(H, LE_RB), 4)), (unsigned)N);
             unsigned int* ws = nullptr;
             if (hist) {
@@ -700,7 +812,8 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
             }
             static const bool big_lds = [] {          // up to 128 KB of staged rows (the default cap is 64 KB): every instantiation launched below
                 bool ok = true;
-#define MSPL_LE_ATTR(CM, EX, A, B) ok = hipFuncSetAttribute((const void*)label_epilogue_lds_kernel<CM, EX, A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess && ok
+#define MSPL_LE_ATTR(CM, EX, A, B) ok = hipFuncSetAttribute((const void*)label_epilogue_lds_kernel<CM, EX, A, B, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess && \
+                                        hipFuncSetAttribute((const void*)label_epilogue_lds_kernel<CM, EX, A, B, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess && ok
                 MSPL_LE_ATTR(5, true, 0, 0);  MSPL_LE_ATTR(5, true, 132, 68);
                 MSPL_LE_ATTR(13, true, 0, 0); MSPL_LE_ATTR(13, true, 132, 68);
                 MSPL_LE_ATTR(20, true, 0, 0); MSPL_LE_ATTR(20, true, 132, 68);
@@ -710,16 +823,18 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
                 return ok;
             }();
             MSPL_REQUIRE(big_lds || lds <= 64 * 1024, MSPL_ERR_HIP, "label_epilogue: could not raise the dynamic LDS limit");
-#define MSPL_LE_LAUNCH(CM, EX) do { if (wide480) hipLaunchKernelGGL((label_epilogue_lds_kernel<CM, EX, 132, 68>), grid, dim3(256), lds, st_, mainp, aux, g, st, lut, labels, kld, ws); \
-                                   else hipLaunchKernelGGL((label_epilogue_lds_kernel<CM, EX, 0, 0>), grid, dim3(256), lds, st_, mainp, aux, g, st, lut, labels, kld, ws); } while (0)
+#define MSPL_LE_KERNEL(CM, EX, A, B) do { if (planes) hipLaunchKernelGGL((label_epilogue_lds_kernel<CM, EX, A, B, true>), grid, dim3(256), lds, st_, mainp, aux, g, st, lp, lut, labels, kld, ws); \
+                                         else hipLaunchKernelGGL((label_epilogue_lds_kernel<CM, EX, A, B, false>), grid, dim3(256), lds, st_, mainp, aux, g, st, lp, lut, labels, kld, ws); } while (0)
+#define MSPL_LE_LAUNCH(CM, EX) do { if (wide480) MSPL_LE_KERNEL(CM, EX, 132, 68); else MSPL_LE_KERNEL(CM, EX, 0, 0); } while (0)
             const bool wide480 = (C == 5 || C == 13 || C == 20) && st.wms == 132 && (!aux || st.was == 68);     // the x2 / x4 heads of 480-pixel-wide images
             if (C == 5) MSPL_LE_LAUNCH(5, true);
             else if (C == 13) MSPL_LE_LAUNCH(13, true);
             else if (C == 20) MSPL_LE_LAUNCH(20, true);
-            else if (C <= 8) { if (wide480) return MSPL_ERR_UNSUPPORTED; hipLaunchKernelGGL((label_epilogue_lds_kernel<8, false, 0, 0>), grid, dim3(256), lds, st_, mainp, aux, g, st, lut, labels, kld, ws); }
-            else if (C <= 16) hipLaunchKernelGGL((label_epilogue_lds_kernel<16, false, 0, 0>), grid, dim3(256), lds, st_, mainp, aux, g, st, lut, labels, kld, ws);
-            else hipLaunchKernelGGL((label_epilogue_lds_kernel<24, false, 0, 0>), grid, dim3(256), lds, st_, mainp, aux, g, st, lut, labels, kld, ws);
+            else if (C <= 8) { if (wide480) return MSPL_ERR_UNSUPPORTED; MSPL_LE_KERNEL(8, false, 0, 0); }
+            else if (C <= 16) MSPL_LE_KERNEL(16, false, 0, 0);
+            else MSPL_LE_KERNEL(24, false, 0, 0);
 #undef MSPL_LE_LAUNCH
+#undef MSPL_LE_KERNEL
             MSPL_CHECK_LAUNCH("label_epilogue");
             if (hist) {
                 hipLaunchKernelGGL(label_hist_reduce_kernel, dim3(LE_RED), dim3(256), 0, st_, ws, (int)le_blocks(N, H, W), ncls, hist);
@@ -727,7 +842,7 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
             }
             return MSPL_OK;
         }
-        MSPL_REQUIRE(!hist, MSPL_ERR_UNSUPPORTED, "label_epilogue_hist: tile does not fit the LDS-staged form (N=%d C=%d %dx%d -> %dx%d)",
+        MSPL_REQUIRE(!hist && !planes, MSPL_ERR_UNSUPPORTED, "label_epilogue_hist: tile does not fit the LDS-staged form (N=%d C=%d %dx%d -> %dx%d)",
                      N, C, Hm, Wm, H, W);
         const dim3 grid((unsigned)ceil_div(W, 256), (unsigned)(4 * ceil_div(H, 4)), (unsigned)N);     // row slots: see the kernel
         MSPL_REQUIRE(H <= 65535, MSPL_ERR_BAD_SHAPE, "label_epilogue: %d rows", H);
@@ -737,7 +852,7 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
         MSPL_CHECK_LAUNCH("label_epilogue");
         return MSPL_OK;
     }
-    MSPL_REQUIRE(!hist, MSPL_ERR_UNSUPPORTED, "label_epilogue_hist: shape outside the label-pass form (N=%d C=%d H=%d)", N, C, H);
+    MSPL_REQUIRE(!hist && !planes, MSPL_ERR_UNSUPPORTED, "label_epilogue_hist: shape outside the label-pass form (N=%d C=%d H=%d)", N, C, H);
     hipLaunchKernelGGL(label_epilogue_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, st_,
                        mainp, aux, g, lut, labels, prob, kld, main_up, aux_up, total);
     MSPL_CHECK_LAUNCH("label_epilogue");
@@ -782,6 +897,34 @@ extern "C" int mspl_label_epilogue_hist_fwd(const float* mainp, const float* aux
                  "use label_epilogue + merge_labels)", C);
     return label_epilogue_impl(mainp, aux, N, C, Hm, Wm, Ha, Wa, H, W, lut, labels, nullptr, kld, nullptr, nullptr, hist, num_classes,
                                workspace, workspace_bytes, stream);
+}
+
+extern "C" int mspl_label_epilogue_planes_fits(int32_t N, int32_t P, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa,
+                                               int32_t H, int32_t W) {
+    if (P < 4 || P > 16 || (P & 3) != 0) return 0;
+    if (!mspl_label_epilogue_hist_fits(N, C, Hm, Wm, Ha, Wa, H, W)) return 0;
+    return (int64_t)N * P * Hm * Wm < (1ll << 31) && (int64_t)N * P * (int64_t)Ha * Wa < (1ll << 31);
+}
+
+extern "C" int mspl_label_epilogue_planes_fwd(const float* main_planes, const float* main_w, const float* main_b,
+                                              const float* aux_planes, const float* aux_w, const float* aux_b, int32_t N, int32_t P,
+                                              int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
+                                              const uint8_t* lut, uint8_t* labels, float* kld, unsigned long long* hist,
+                                              int32_t num_classes, void* workspace, int64_t workspace_bytes, void* stream) {
+    MSPL_REQUIRE(main_planes && main_w && main_b && labels, MSPL_ERR_NULL_POINTER, "label_epilogue_planes: null pointer");
+    MSPL_REQUIRE(!aux_planes || (aux_w && aux_b), MSPL_ERR_NULL_POINTER, "label_epilogue_planes: aux head without its classifier");
+    MSPL_REQUIRE(!hist || (num_classes >= 1 && num_classes <= 32), MSPL_ERR_UNSUPPORTED, "label_epilogue_planes: %d classes (1..32)",
+                 num_classes);
+    if (!aux_planes) Ha = Wa = 0;
+    MSPL_REQUIRE(N > 0 && P > 0 && C > 0 && Hm > 0 && Wm > 0 && H > 0 && W > 0 && Ha >= 0 && Wa >= 0, MSPL_ERR_BAD_SHAPE,
+                 "label_epilogue_planes: bad shape N=%d P=%d C=%d main=%dx%d aux=%dx%d out=%dx%d", N, P, C, Hm, Wm, Ha, Wa, H, W);
+    MSPL_REQUIRE(mspl_label_epilogue_planes_fits(N, P, C, Hm, Wm, Ha, Wa, H, W), MSPL_ERR_UNSUPPORTED,
+                 "label_epilogue_planes: shape outside the planes form (N=%d P=%d C=%d %dx%d -> %dx%d): run the classifier "
+                 "and mspl_label_epilogue_fwd", N, P, C, Hm, Wm, H, W);
+    LePlanes lp;
+    lp.wm = main_w; lp.bm = main_b; lp.wa = aux_w; lp.ba = aux_b; lp.P = P;
+    return label_epilogue_impl(main_planes, aux_planes, N, C, Hm, Wm, Ha, Wa, H, W, lut, labels, nullptr, kld, nullptr, nullptr, hist,
+                               hist ? num_classes : 0, workspace, workspace_bytes, stream, &lp);
 }
 
 extern "C" int mspl_merge_labels_fwd(const uint8_t* const* src, int32_t S, int64_t npix, int32_t num_classes,

@@ -14,6 +14,8 @@ BatchNorm runs in eval mode (running statistics), which is what the label pass a
 self-training loop use (uest_seg_multi_os.py:605-608); it is folded into per-channel scale/shift
 vectors that are cached until a parameter changes.
 """
+import contextlib
+import gc
 import math
 import os
 import weakref
@@ -166,6 +168,24 @@ def join(idx, outputs=()):
         t.record_stream(cur)
 
 
+@contextlib.contextmanager
+def graph_capture(graph, **kw):
+    """torch.cuda.graph(graph, **kw) with the garbage collector kept out of the capture.  A dead reference cycle may hold a
+    CUDAGraph (a step or pass object that was replaced) whose destructor frees the graph's memory pool -- a call the runtime
+    forbids while a capture is under way: the process aborts when the collector happens to run inside one (seen in the backward
+    of a captured training step, on the autograd thread; torch >= 2.9 no longer collects on entering a capture).  So: collect
+    first, where freeing is legal, and keep the automatic collector off until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
+
 def _training_path():
     """True when gradients are enabled: the modules then run the autograd form (HIP forward + HIP backward per op,
     mspl_amd/autograd.py) instead of the fused inference kernels."""
@@ -200,6 +220,9 @@ _CONV_SKIP = os.environ.get('MSPL_CONV_SKIP', '1') != '0'      # EESP in train()
 _FUSED_BN_TRAIN = os.environ.get('MSPL_FUSED_BN_TRAIN', '1') != '0'      # batch-statistics BN + PReLU as one autograd node
 _FUSED_DW_EXP = os.environ.get('MSPL_EESP_EXP', '1') != '0'   # inference: K2 + K3 of a stride-1 EESP block as one launch
 _FUSED_DOWN_HEAD = os.environ.get('MSPL_DOWN_HEAD', '1') != '0'   # inference: a DownSampler's projection + pool + plane sums as one launch (ops.down_head)
+# label pass: the final 1x1 classifier of a decoder head (EfficientPyrPool, last_layer_br=False) is computed by the label epilogue
+# from the head's planes (ops.label_epilogue_planes) instead of a launch of its own
+_FUSED_HEAD_CLASSIFIER = os.environ.get('MSPL_HEAD_CLASSIFIER', '1') != '0'
 _FUSED_DEC_MERGE = True          # inference: skip 3x3 + up-merge + the next pyramid block's projection as one launch (ops.decoder_merge)
 _FUSED_NEXT_PROJ = os.environ.get('MSPL_EESP_NEXT', '1') != '0'   # ... and the following block's proj_1x1 inside that launch
 _FUSED_EESP_TRAIN = os.environ.get('MSPL_FUSED_EESP_TRAIN', '1') != '0'  # EESP block as one autograd node (frozen BatchNorm)
@@ -799,8 +822,10 @@ class EfficientPyrPool(nn.Module):
             return ag.conv_affine_prelu(out, conv.weight, 1, 1, None, conv.bias, None)
         return ag.affine_prelu(ag.conv(out, conv.weight, 1, 1), None, conv.bias, None)
 
-    def forward(self, x, fused=True, projected=False):
-        """projected=True (inference only): x is already projection_layer's output (decoder_stage_fused)."""
+    def forward(self, x, fused=True, projected=False, planes=False):
+        """projected=True (inference only): x is already projection_layer's output (decoder_stage_fused).
+        planes=True (inference only, heads without the final BN + PReLU): leave merge_layer[3] to the consumer -- returns
+        (planes, weight, bias) for ops.label_epilogue_planes when the switch _FUSED_HEAD_CLASSIFIER is on, the logits otherwise."""
         if _training_path():
             return self._forward_train(x)
         if not projected:
@@ -811,6 +836,8 @@ class EfficientPyrPool(nn.Module):
         ok = fused and self._fusable(sizes, height, width) and all(
             (s >= 1.0) or (hs <= height and ws <= width) for s, (hs, ws) in zip(self.scales, sizes))
         m = self.forward_fused(x, sizes) if ok else self.forward_unfused(x)
+        if planes and _FUSED_HEAD_CLASSIFIER and not self.last_layer_br:
+            return m, self.merge_layer[3].weight, self.merge_layer[3].bias
         return ops.conv1x1(m, self.merge_layer[3].weight, 1, self._final_epilogue())
 
 

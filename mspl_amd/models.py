@@ -214,7 +214,8 @@ class _SegBase(nn.Module):
             l4 = self.fusion_gate_level4(l4, dl4)                               # :261-264
         return l1, l2, l3, l4
 
-    def _decode(self, l1, l2, l3, l4, aux_layer):
+    def _decode(self, l1, l2, l3, l4, aux_layer, planes=False):
+        """planes=True (inference): the two heads stay in front of their classifier, see EfficientPyrPool.forward."""
         aux = None
         # the three skip connections depend on the encoder only, the auxiliary head on one decoder stage only: both
         # are issued on side streams (layers.fork / join) and overlap the main decoder chain
@@ -239,33 +240,33 @@ class _SegBase(nn.Module):
         bu = self.bu_dec_l1(l4)
         if aux_layer == 0:
             with fork(2, (bu,)):
-                aux = self.aux_decoder(bu)
+                aux = self.aux_decoder(bu, planes=planes)
         wait_mark(e2, (pw2,))
         bu = self._decode_stage(st2, l3, pw2, bu)
         if aux_layer == 1:
             with fork(2, (bu,)):
-                aux = self.aux_decoder(bu)
+                aux = self.aux_decoder(bu, planes=planes)
         wait_mark(e3, (pw3,))
         bu = self._decode_stage(st3, l2, pw3, bu)
         if aux_layer == 2:
             with fork(2, (bu,)):
-                aux = self.aux_decoder(bu)
+                aux = self.aux_decoder(bu, planes=planes)
         wait_mark(e4, (pw4,))                                     # the side stream's last work: it is joined here
-        bu = self._decode_stage(st4, l1, pw4, bu)
-        join(2, (aux,))
+        bu = self._decode_stage(st4, l1, pw4, bu, planes)
+        join(2, (aux[0] if isinstance(aux, tuple) else aux,))
         return bu, aux
 
     @staticmethod
-    def _decode_stage(st, enc, pw, bu):
+    def _decode_stage(st, enc, pw, bu, planes=False):
         """bu_dec_lK(bu_br_lK(merge_enc_dec_lK(enc) + upsample(bu))), espdnet_ue.py:276-299.  pw: the skip connection's output
         (N, dec, H, W), or -- a 2-d (N, dec) tensor -- only its gate: the head of the stage then runs as one launch."""
         merge, br, pyr = st
         if pw.dim() == 2:
             proj = decoder_stage_fused(merge, enc, pw, bu, br, pyr)
             if proj is not None:
-                return pyr(proj, projected=True)
+                return pyr(proj, projected=True, planes=planes)
             pw = merge.expand(enc, pw)                            # the library declined the shape after all
-        return pyr(decoder_merge(pw, bu, br))
+        return pyr(decoder_merge(pw, bu, br), planes=planes)
 
     def get_basenet_params(self):
         return _param_gen([self.base_net])
@@ -327,6 +328,18 @@ class ESPDNetwithUncertaintyEstimation(_SegBase):
         l1, l2, l3, l4 = self._encode_rgbd(x, x_d)
         return self._decode(l1, l2, l3, l4, self.aux_layer)
 
+    def forward_lowres_planes(self, x, x_d=None, pyr=None):
+        """forward_lowres for the label pass (inference only): each head comes back in front of its final 1x1 classifier, as
+        (planes, weight, bias) for ops.label_epilogue_planes -- or as its logits where layers._FUSED_HEAD_CLASSIFIER is off."""
+        if _training_path():
+            raise RuntimeError('mspl_amd: forward_lowres_planes is an inference path (run it under torch.no_grad())')
+        _check_input(x)
+        if x_d is None:
+            l1, l2, l3, l4 = self._encode(x, True, self.depth_base_net.level3, pyr)
+        else:
+            l1, l2, l3, l4 = self._encode_rgbd(x, x_d)
+        return self._decode(l1, l2, l3, l4, self.aux_layer, planes=True)
+
     def forward(self, x, x_d=None):
         main, aux = self.forward_lowres(x, x_d)
         if _training_path():
@@ -368,6 +381,17 @@ class ESPDNetSegmentation(_SegBase):
             l1, l2, l3, l4 = self._encode_rgbd(x, x_d)
         return self._decode(l1, l2, l3, l4, -1)[0], None
 
+    def forward_lowres_planes(self, x, x_d=None):
+        """forward_lowres with the head in front of its final 1x1 classifier (see ESPDNetwithUncertaintyEstimation)."""
+        if _training_path():
+            raise RuntimeError('mspl_amd: forward_lowres_planes is an inference path (run it under torch.no_grad())')
+        _check_input(x)
+        if x_d is None:
+            l1, l2, l3, l4 = self._encode(x, True, self.depth_base_net.level3)
+        else:
+            l1, l2, l3, l4 = self._encode_rgbd(x, x_d)
+        return self._decode(l1, l2, l3, l4, -1, planes=True)[0], None
+
     def forward(self, x, x_d=None):
         main, _ = self.forward_lowres(x, x_d)
         if _training_path():
@@ -389,6 +413,14 @@ class ESPNetv2Segmentation(_SegBase):
         # level2_0 is called WITHOUT the image (espnetv2.py:127)
         l1, l2, l3, l4 = self._encode(x, False, self.base_net.level3)
         return self._decode(l1, l2, l3, l4, -1)[0], None
+
+    def forward_lowres_planes(self, x):
+        """forward_lowres with the head in front of its final 1x1 classifier (see ESPDNetwithUncertaintyEstimation)."""
+        if _training_path():
+            raise RuntimeError('mspl_amd: forward_lowres_planes is an inference path (run it under torch.no_grad())')
+        _check_input(x)
+        l1, l2, l3, l4 = self._encode(x, False, self.base_net.level3)
+        return self._decode(l1, l2, l3, l4, -1, planes=True)[0], None
 
     def forward(self, x):
         main, _ = self.forward_lowres(x)

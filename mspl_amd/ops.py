@@ -684,6 +684,57 @@ def label_epilogue_hist(main, aux, size, hist, num_classes, lut=None, want_kld=F
     return res
 
 
+def _head_planes(head, what):
+    """A head before its classifier, (planes (N,P,h,w), weight (C,P[,1,1]), bias (C)) -> checked fp32 tensors and (N, P, C, h, w)."""
+    planes, weight, bias = head
+    planes, weight, bias = _f32(planes, what + ' planes'), _f32(weight, what + ' weight'), _f32(bias, what + ' bias')
+    N, P, h, w = [int(v) for v in planes.shape]
+    C = int(weight.shape[0])
+    if weight.numel() != C * P or bias.numel() != C:
+        raise RuntimeError('mspl_amd: %s classifier %s / bias %s does not match %d planes' %
+                           (what, tuple(weight.shape), tuple(bias.shape), P))
+    return planes, weight, bias, (N, P, C, h, w)
+
+
+def label_epilogue_planes_fits(main, aux, size):
+    """True when label_epilogue_planes covers these heads; main / aux: (planes, weight, bias), aux may be None."""
+    N, P, Hm, Wm = [int(v) for v in main[0].shape]
+    C = int(main[1].shape[0])
+    Ha, Wa = ([int(v) for v in aux[0].shape[2:]] if aux is not None else (0, 0))
+    if aux is not None and (int(aux[0].shape[1]) != P or int(aux[1].shape[0]) != C):
+        return False
+    return bool(lib.mspl_label_epilogue_planes_fits(N, P, C, Hm, Wm, Ha, Wa, int(size[0]), int(size[1])))
+
+
+def label_epilogue_planes(main, aux, size, hist=None, num_classes=0, lut=None, want_kld=False):
+    """K8+K9 from the heads' planes: the final 1x1 classifier of both heads is computed inside the epilogue (the logits are never
+    written).  main / aux: (planes (N,P,h,w), weight (C,P,1,1), bias (C)); aux may be None.  With hist: label_epilogue_hist's
+    histogram contract.  Equals conv1x1 + label_epilogue[_hist] bit for bit.  Returns dict(labels[, kld])."""
+    mp, mw, mbias, (N, P, C, Hm, Wm) = _head_planes(main, 'main')
+    ap = aw = abias = None
+    Ha = Wa = 0
+    if aux is not None:
+        ap, aw, abias, (Na, Pa, Ca, Ha, Wa) = _head_planes(aux, 'aux')
+        if (Na, Pa, Ca) != (N, P, C):
+            raise RuntimeError('mspl_amd: aux head (N=%d, P=%d, C=%d) does not match main (N=%d, P=%d, C=%d)' % (Na, Pa, Ca, N, P, C))
+    H, W = int(size[0]), int(size[1])
+    if hist is not None and (hist.dtype != torch.int64 or not hist.is_cuda or hist.numel() < num_classes):
+        raise RuntimeError('mspl_amd: hist must be a CUDA int64 tensor with >= num_classes entries')
+    if lut is not None and (lut.dtype != torch.uint8 or not lut.is_cuda or lut.numel() < C):
+        raise RuntimeError('mspl_amd: lut must be a CUDA uint8 tensor with >= %d entries' % C)
+    res = {'labels': torch.empty((N, H, W), device=mp.device, dtype=torch.uint8)}
+    if want_kld:
+        res['kld'] = torch.empty((N, H, W), device=mp.device, dtype=torch.float32)
+    ws, nbytes = None, 0
+    if hist is not None:
+        nbytes = int(lib.mspl_label_epilogue_hist_workspace_bytes(N, H, W))
+        ws = torch.empty(max(nbytes, 4), device=mp.device, dtype=torch.uint8)       # per-workgroup partial histograms
+    check(lib.mspl_label_epilogue_planes_fwd(_p(mp), _p(mw), _p(mbias), _p(ap), _p(aw), _p(abias), N, P, C, Hm, Wm, Ha, Wa, H, W,
+                                             _p(lut), _p(res['labels']), _p(res.get('kld')), _p(hist), int(num_classes), _p(ws),
+                                             nbytes, _stream()))
+    return res
+
+
 def merge_labels(sources, num_classes, thresh, fill=4, hist=None):
     """K10.  sources: list of uint8 CUDA tensors of identical shape.  hist: uint64-as-int64 CUDA tensor of
     num_classes entries, accumulated into (caller zeroes), or None."""

@@ -332,7 +332,7 @@ class GraphedSupervisedStep:
             self.cw = criterion.class_wts.detach().to(self.inputs.device, torch.float32).clone()
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with layers.graph_capture(self.graph):
             self.optimizer.zero_grad()
             with torch.enable_grad(), ag.grad_sinks(), self.optimizer.transposer.active():
                 layers.prefold_frozen_bn(model)

@@ -240,7 +240,7 @@ class GraphedTrainStep:
         tr = self.optimizer.transposer
         if self.lanes == 1:
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with layers.graph_capture(self.graph):
                 self.optimizer.zero_grad()
                 with torch.enable_grad(), ag.grad_sinks(), tr.active():
                     layers.prefold_frozen_bn(model)
@@ -250,7 +250,7 @@ class GraphedTrainStep:
             # what every lane needs first: zeroed gradients, this step's transposed weights and folded BatchNorms (their tensors live
             # in this graph's pool, the lanes' graphs read them)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with layers.graph_capture(self.graph):
                 self.optimizer.zero_grad()
                 tr.run()
                 with torch.no_grad():
@@ -269,7 +269,7 @@ class GraphedTrainStep:
                 for i, st in enumerate(self.streams):
                     st.wait_stream(torch.cuda.current_stream())
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=st):
+                    with layers.graph_capture(g, stream=st):
                         with torch.enable_grad(), ag.grad_sinks(), tr.active(refresh=False):
                             loss = forward_loss(model, self.images[i * b:(i + 1) * b], self.labels[i * b:(i + 1) * b], self.cw, ce_scale,
                                                 out_scale=1.0 / self.lanes, root=True, meters=meters)

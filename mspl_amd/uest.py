@@ -42,6 +42,22 @@ def _lowres(model, image, pyr=None):
     return out if isinstance(out, tuple) else (out, None)
 
 
+def _lowres_planes(model, image, pyr=None):
+    """_lowres for a consumer that can take the heads in front of their final 1x1 classifier (ops.label_epilogue_planes): each
+    head is then (planes, weight, bias); logits as from _lowres where the model or layers._FUSED_HEAD_CLASSIFIER says otherwise."""
+    fn = getattr(model, 'forward_lowres_planes', None) if layers._FUSED_HEAD_CLASSIFIER else None
+    if fn is None:
+        return _lowres(model, image, pyr)
+    return fn(image, pyr=pyr) if pyr is not None else fn(image)
+
+
+def _head_logits(head):
+    """The logits of a head from _lowres_planes: the classifier launch the planes form leaves out (a tensor passes through)."""
+    if isinstance(head, tuple):
+        return ops.conv1x1(head[0], head[1], 1, ops.Epi(shift=head[2]))
+    return head
+
+
 def _lowres_batch_stats(model, images, pyr=None):
     """`--eval-training` label generation (uest_seg_multi_os.py:749-752, 871-876): the model is in train() mode under no_grad, so
     every BatchNorm normalises with the statistics of ITS OWN batch -- and the reference's loader has batch size 1 (:746), so the
@@ -167,7 +183,7 @@ class _GraphedPassMixin:
             for t, b in zip(state, before):
                 t.copy_(b)
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode='thread_local'):      # other threads (the PNG writer) keep using HIP
+            with layers.graph_capture(graph, capture_error_mode='thread_local'):      # other threads (the PNG writer) keep using HIP
                 static_out = self._graph_outputs(self._run(static_in))
             for t, b in zip(state, before):           # capture does not execute, but keep the invariant explicit
                 t.copy_(b)
@@ -262,7 +278,11 @@ class PseudoLabelPass(_GraphedPassMixin):
         for m, lut in zip(self.models, self.luts):
             # (sources run one after the other: forking one HIP stream per source model on top of the models' own side
             # streams crashed hipStreamEndCapture on ROCm 7.2 -- nested fork/join graphs are avoided)
-            main, aux = _lowres(m, images, pyr)
+            main, aux = _lowres_planes(m, images, pyr)
+            if isinstance(main, tuple) and ops.label_epilogue_planes_fits(main, aux, images.shape[2:]):
+                maps.append(ops.label_epilogue_planes(main, aux, images.shape[2:], lut=lut)['labels'])
+                continue
+            main, aux = _head_logits(main), _head_logits(aux)
             maps.append(ops.label_epilogue(main, aux, images.shape[2:], lut=lut)['labels'])
         return ops.merge_labels(maps, self.classes, self.thresh, NO_AGREEMENT_CLASS, self.hist), maps
 
@@ -665,7 +685,14 @@ class SelfLabelPass(_GraphedPassMixin):
         self.hist.zero_()
 
     def _run(self, images):
-        main, aux = _lowres_batch_stats(self.model, images) if self.eval_training else _lowres(self.model, images)
+        main, aux = _lowres_batch_stats(self.model, images) if self.eval_training else _lowres_planes(self.model, images)
+        if isinstance(main, tuple):
+            # the heads in front of their classifier: the epilogue forms the logits itself (no classifier launches, no logits
+            # written) under the conditions of the histogram form below
+            if main[1].shape[0] <= min(24, self.classes, 32) and ops.label_epilogue_planes_fits(main, aux, images.shape[2:]):
+                r = ops.label_epilogue_planes(main, aux, images.shape[2:], self.hist, self.classes, want_kld=self.with_kld)
+                return r['labels'], r.get('kld')
+            main, aux = _head_logits(main), _head_logits(aux)
         if main.shape[1] <= min(24, self.classes, 32) and ops.label_epilogue_hist_fits(main, aux, images.shape[2:]):
             # every argmax is a counted class: the epilogue kernel accumulates the histogram itself (one launch; the S = 1 merge
             # would be the identity on these labels)
