@@ -42,7 +42,7 @@ class TrainRec(ctypes.Structure):
 FILTER_LANCZOS = 1              # MSPL_FILTER_LANCZOS
 FILTER_BILINEAR = 2             # MSPL_FILTER_BILINEAR
 
-ABI_VERSION = 4                 # include/mspl_hip.h: mspl_abi_version()
+ABI_VERSION = 5                 # include/mspl_hip.h: mspl_abi_version()
 ERR_UNSUPPORTED = -2            # MSPL_ERR_UNSUPPORTED
 # mspl_wgrad_form_t: what mspl_conv_bwd_weight_plan reports
 WGRAD_1X1_MFMA, WGRAD_1X1_LDS, WGRAD_STEM_S2_STRIP, WGRAD_STEM_COB4, WGRAD_STRIP, WGRAD_G3X3, WGRAD_GENERIC = range(1, 8)
@@ -112,7 +112,7 @@ SIGNATURES = {
     'mspl_affine_prelu_bwd': [c_f32p] * 7 + [c_i32] * 3 + [c_f32p] * 5 + [ctypes.c_void_p],
     'mspl_bn_train_small_fits': [c_i32] * 3,
     'mspl_bn_train_small_fwd': [c_f32p] * 5 + [c_i32] * 3 + [ctypes.c_float] * 2 + [c_f32p] * 2 + [ctypes.c_void_p] + [c_f32p] * 5 + [ctypes.c_void_p],
-    'mspl_bn_train_small_bwd': [c_f32p] * 9 + [c_i32] * 4 + [c_f32p] * 5 + [ctypes.c_void_p],
+    'mspl_bn_train_small_bwd': [c_f32p] * 9 + [c_i32] * 3 + [ctypes.c_float, c_i32] + [c_f32p] * 5 + [ctypes.c_void_p],
     'mspl_bn_train_prelu_bwd_apply': [c_f32p] * 7 + [c_i32] * 3 + [c_f32p, ctypes.c_void_p],
     'mspl_pyrpool_merge_fwd': [c_f32p] + [c_i32] * 5 + [c_f32p] * 5 + [ctypes.c_void_p],
     'mspl_bn_stats_path_add': [c_f32p] * 4 + [c_i32] * 4 + [ctypes.c_void_p],

@@ -1438,6 +1438,7 @@ class BNTrainPReLUFn(torch.autograd.Function):
         residual = None if residual is None else _c(residual)
         gamma_c = _c(gamma)
         y, st, ctx.small = _bn_train_forward(z, residual, gamma_c, _c(beta), alpha, running_mean, running_var, eps, momentum, ws, nbt)
+        ctx.eps = eps
         ctx.save_for_backward(z, gamma_c, alpha, residual, st, ws)
         ctx.g_bn, ctx.g_alpha = GradDstPair(gamma, beta), GradDst(alpha)
         return y
@@ -1456,7 +1457,7 @@ class BNTrainPReLUFn(torch.autograd.Function):
         if ctx.small:
             gz = torch.empty_like(z)
             check(lib.mspl_bn_train_small_bwd(_p(z), _p(residual), _p(gy), _p(scale), _p(shift), _p(alpha), _p(gamma), _p(mean), _p(invstd),
-                                              N, C, hw, direct, _p(gz), _p(gres), _p(d_gamma), _p(d_beta), _p(gal), _stream()))
+                                              N, C, hw, ctx.eps, direct, _p(gz), _p(gres), _p(d_gamma), _p(d_beta), _p(gal), _stream()))
         else:
             gc = torch.empty_like(z) if residual is not None else None       # no residual: the second pass recomputes it from (z, gy)
             check(lib.mspl_bn_train_prelu_bwd(_p(z), _p(residual), _p(gy), _p(scale), _p(shift), _p(alpha), _p(gamma), _p(mean), _p(invstd),

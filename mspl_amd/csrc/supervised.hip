@@ -99,7 +99,12 @@ __global__ __launch_bounds__(256) void bn_stats_fused_kernel(const float* __rest
     long long u = u0 + threadIdx.x;
     int n = (int)(u / L), q = (int)(u - (long long)n * L);
     auto advance = [&]() { u += 256; q += step_q; n += step_n; if (q >= L) { q -= L; ++n; } };
+    // float32 for at most 16 terms, then double: a thread's share has no upper limit here (parts = 1 from 768 channels on: 160 and more
+    // terms), and with k an outlier (|k - mean| = 40 std) every term of s2 is 1600 var -- 160 of them in float32 cost the variance 4e-5
+    // relative, more than the fold's own rounding allows the largest |y| (tests/test_gpu_bn_conditioning.py, t_parts1)
     float s1 = 0.f, s2 = 0.f;
+    double d1 = 0.0, d2 = 0.0;
+    auto flush = [&]() { d1 += (double)s1;  d2 += (double)s2;  s1 = 0.f;  s2 = 0.f; };
     if (vec) {
         auto acc4 = [&](const float4& v) {
             const float a = v.x - k, b = v.y - k, cc = v.z - k, d = v.w - k;
@@ -113,21 +118,24 @@ __global__ __launch_bounds__(256) void bn_stats_fused_kernel(const float* __rest
             const float4* p3 = reinterpret_cast<const float4*>(z + ((size_t)n * C + c) * (size_t)HW) + q;  advance();
             const float4 v0 = *p0, v1 = *p1, v2 = *p2, v3 = *p3;
             acc4(v0); acc4(v1); acc4(v2); acc4(v3);
+            flush();
         }
-        while (u < u1) {
+        while (u < u1) {                            // (at most three quads)
             const float4 v = reinterpret_cast<const float4*>(z + ((size_t)n * C + c) * (size_t)HW)[q];
             advance();
             acc4(v);
         }
     } else {
+        int held = 0;
         while (u < u1) {
             const float a = z[((size_t)n * C + c) * (size_t)HW + q] - k;
             advance();
             s1 += a;
             s2 += a * a;
+            if (++held == 16) { flush();  held = 0; }
         }
     }
-    double d1 = s1, d2 = s2;
+    flush();
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         d1 += __shfl_down(d1, o, 64);
@@ -227,7 +235,7 @@ __global__ __launch_bounds__(256) void bn_stats_path_add_kernel(float* __restric
 // ---- small planes (levels 3-5: N * HW <= ~40 k values per channel): the whole BatchNorm + PReLU node of a channel in ONE workgroup and
 // ONE launch each way.  Forward: shifted sums of the channel (fp32 per thread, double across the workgroup), mean / invstd / fold /
 // running statistics, then the apply pass over the same values (L2 hits); backward: the three channel sums, (d gamma, d beta, p, q),
-// then gz = p * z + q + direct gradient.  No atomics, no workspace, no second launch: at these sizes the two-launch forms are four
+// then gz = p * z + q + direct gradient (channels of one or two values: bn_train_few_bwd_kernel, that path centred and in double).  No atomics, no workspace, no second launch: at these sizes the two-launch forms are four
 // launch latencies for ~2 us of data movement each (45 of the supervised iteration's 70 BatchNorms).
 __device__ __forceinline__ double bn_block_sum(double v, double* part) {
 #pragma unroll
@@ -442,6 +450,128 @@ __global__ __launch_bounds__(1024) void bn_train_small_bwd_kernel(const float* _
     }
 }
 
+// The same node for channels of at most BN_FEW_VALUES (two) values: the statistics path in DOUBLE.
+__global__ __launch_bounds__(256) void bn_train_few_bwd_kernel(const float* __restrict__ z, const float* __restrict__ res,
+                                                                 const float* __restrict__ gy, const float* __restrict__ scale,
+                                                                 const float* __restrict__ shift, const float* __restrict__ alpha,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                                 int N, int C, int HW, float eps,
+                                                                 int accumulate, float* __restrict__ gz, float* __restrict__ gres,
+                                                                 float* __restrict__ ggamma, float* __restrict__ gbeta,
+                                                                 float* __restrict__ galpha) {
+    __shared__ double part[16];
+    __shared__ double coef[4];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const bool vec = (HW & 3) == 0;
+    const int L = vec ? (HW >> 2) : HW, total = N * L;
+    const int NT = blockDim.x;                  // 256
+    const int step_n = NT / L, step_q = NT - step_n * L;
+    const float sc = scale[c], sh = shift[c];
+    const bool act = alpha != nullptr;
+    const float al = act ? alpha[c] : 1.f;
+    // The statistics path runs in DOUBLE on centred values, from the channel's own moments taken again here (shifted by the forward's
+    // float32 mean): with two values per channel xhat is +-1 whatever z is, and gz = scale (g' - mean g' - xhat mean(g' xhat)) cancels to
+    // eps / var of its terms (M - 2 = 0 degrees of freedom).  A float32 evaluation -- or a double one on the forward's ROUNDED invstd --
+    // is off by 2^-24 of a term, any multiple of the true value: 7 x the bound against float64 (tests/test_gpu_bn_conditioning.py,
+    // s_L1_scalar).  One or two values in the whole channel: the double operations cost nothing.  The PReLU branch is the forward's
+    // float32 expression.  (Written for any size; every larger channel keeps the float32 kernel above, whose results it would move.)
+    const double mu = (double)mean[c];
+    double a1 = 0.0, a2 = 0.0, s_scale = 0.0, s_shift = 0.0, s_alpha = 0.0;
+    auto gprime = [&](float zv, float rv, float g, bool& neg) {      // gradient of the pre-activation, as affine_prelu_bwd_kernel
+        const float u = fmaf(zv, sc, sh) + rv;          // the forward's expression (one fused multiply-add, then the residual): same PReLU branch
+        neg = act && u <= 0.f;
+        return u;
+    };
+    auto sums = [&](float zv, float rv, float g) {
+        bool neg;
+        const float u = gprime(zv, rv, g, neg);
+        if (neg) s_alpha += (double)(g * u);
+        const double gd = neg ? (double)al * (double)g : (double)g;
+        const double d = (double)zv - mu;
+        a1 += d;
+        a2 = fma(d, d, a2);
+        s_shift += gd;
+        s_scale = fma(gd, d, s_scale);
+    };
+    {
+        int u = tid, n = u / L, q = u - n * L;
+        auto advance = [&]() { u += NT; q += step_q; n += step_n; if (q >= L) { q -= L; ++n; } };
+        if (vec) {
+            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+            while (u < total) {
+                const size_t oa = ((size_t)n * C + c) * (size_t)HW + 4 * (size_t)q;
+                advance();
+                const bool hb = u < total;
+                const size_t ob = hb ? ((size_t)n * C + c) * (size_t)HW + 4 * (size_t)q : oa;
+                advance();
+                const float4 za = *reinterpret_cast<const float4*>(z + oa), ga = *reinterpret_cast<const float4*>(gy + oa);
+                const float4 zb = *reinterpret_cast<const float4*>(z + ob), gb = *reinterpret_cast<const float4*>(gy + ob);
+                const float4 ra = res ? *reinterpret_cast<const float4*>(res + oa) : zero, rb = res ? *reinterpret_cast<const float4*>(res + ob) : zero;
+                sums(za.x, ra.x, ga.x); sums(za.y, ra.y, ga.y); sums(za.z, ra.z, ga.z); sums(za.w, ra.w, ga.w);
+                if (hb) { sums(zb.x, rb.x, gb.x); sums(zb.y, rb.y, gb.y); sums(zb.z, rb.z, gb.z); sums(zb.w, rb.w, gb.w); }
+            }
+        } else {
+            while (u < total) {
+                const size_t o = ((size_t)n * C + c) * (size_t)HW + q;
+                advance();
+                sums(z[o], res ? res[o] : 0.f, gy[o]);
+            }
+        }
+    }
+    const double A1 = bn_block_sum(a1, part), A2 = bn_block_sum(a2, part), T = bn_block_sum(s_scale, part), S = bn_block_sum(s_shift, part);
+    const double dal = act ? bn_block_sum(s_alpha, part) : 0.0;
+    if (tid == 0) {
+        const double M = (double)N * (double)HW;
+        const double e1 = A1 / M;                             // mean - mu: the rounding of the forward's float32 mean
+        double var = A2 / M - e1 * e1;
+        if (var < 0.0) var = 0.0;
+        const double is = 1.0 / sqrt(var + (double)eps);
+        const double t = T - e1 * S;                          // sum g' (z - mean)
+        const double sd = (double)gamma[c] * is;
+        const float dg = (float)(t * is), db = (float)S;
+        ggamma[c] = accumulate ? ggamma[c] + dg : dg;
+        gbeta[c] = accumulate ? gbeta[c] + db : db;
+        if (galpha && act) galpha[c] += (float)dal;
+        coef[0] = -((sd * is) * is) * t / M;                  // p
+        coef[1] = -(S * sd) / M;                              // q
+        coef[2] = mu + e1;
+        coef[3] = sd;
+    }
+    __syncthreads();
+    const double pc = coef[0], qc = coef[1], md = coef[2], sd = coef[3];
+    auto one = [&](float zv, float rv, float g, float& d) {
+        bool neg;
+        gprime(zv, rv, g, neg);
+        d = neg ? al * g : g;
+        const double gd = neg ? (double)al * (double)g : (double)g;
+        return (float)fma((double)zv - md, pc, fma(gd, sd, qc));
+    };
+    int u = tid, n = u / L, q = u - n * L;
+    auto advance = [&]() { u += NT; q += step_q; n += step_n; if (q >= L) { q -= L; ++n; } };
+    if (vec) {
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        while (u < total) {
+            const size_t oa = ((size_t)n * C + c) * (size_t)HW + 4 * (size_t)q;
+            advance();
+            const float4 za = *reinterpret_cast<const float4*>(z + oa), ga = *reinterpret_cast<const float4*>(gy + oa);
+            const float4 ra = res ? *reinterpret_cast<const float4*>(res + oa) : zero;
+            float4 d, o;
+            o.x = one(za.x, ra.x, ga.x, d.x); o.y = one(za.y, ra.y, ga.y, d.y); o.z = one(za.z, ra.z, ga.z, d.z); o.w = one(za.w, ra.w, ga.w, d.w);
+            if (gres) *reinterpret_cast<float4*>(gres + oa) = d;
+            *reinterpret_cast<float4*>(gz + oa) = o;
+        }
+    } else {
+        while (u < total) {
+            const size_t o = ((size_t)n * C + c) * (size_t)HW + q;
+            advance();
+            float d;
+            const float v = one(z[o], res ? res[o] : 0.f, gy[o], d);
+            if (gres) gres[o] = d;
+            gz[o] = v;
+        }
+    }
+}
+
 // Second pass of the batch-statistics BatchNorm + PReLU backward without a residual: gz = p * z + q + gc with the direct gradient
 // gc = (u > 0 ? gy : alpha * gy) * scale, u = z * scale + shift, RECOMPUTED from (z, gy) instead of read back -- the first pass
 // (mspl_bn_train_prelu_bwd with gc = NULL) then only reads: five tensor passes per BatchNorm instead of six.  Same operations in the
@@ -561,6 +691,9 @@ static int bn_batch_stats_impl(const float* z, int32_t N, int32_t C, int32_t HW,
                                float* running_var, const float* gamma, const float* beta, double* ws, float* mean, float* invstd,
                                float* scale, float* shift, void* stream);
 
+// channels of at most this many VALUES (N * HW) take bn_train_few_bwd_kernel: M - 2 = 0 degrees of freedom, gz vanishes to eps / var
+static const int BN_FEW_VALUES = 2;
+
 extern "C" int mspl_bn_batch_stats_fwd(const float* z, int32_t N, int32_t C, int32_t HW, float eps, float momentum,
                                        float* running_mean, float* running_var, double* ws, float* mean, float* invstd,
                                        void* stream) {
@@ -601,8 +734,8 @@ extern "C" int mspl_bn_train_small_fwd(const float* z, const float* residual, co
 
 extern "C" int mspl_bn_train_small_bwd(const float* z, const float* residual, const float* gy, const float* scale, const float* shift,
                                        const float* alpha, const float* gamma, const float* mean, const float* invstd, int32_t N, int32_t C,
-                                       int32_t HW, int32_t accumulate, float* gz, float* gres, float* ggamma, float* gbeta, float* galpha,
-                                       void* stream) {
+                                       int32_t HW, float eps, int32_t accumulate, float* gz, float* gres, float* ggamma, float* gbeta,
+                                       float* galpha, void* stream) {
     MSPL_REQUIRE(z && gy && scale && shift && gamma && mean && invstd && gz && ggamma && gbeta, MSPL_ERR_NULL_POINTER,
                  "bn_train_small_bwd: null pointer");
     MSPL_REQUIRE((gres == nullptr) || residual, MSPL_ERR_NULL_POINTER, "bn_train_small_bwd: gres without residual");
@@ -611,8 +744,12 @@ extern "C" int mspl_bn_train_small_bwd(const float* z, const float* residual, co
                  MSPL_ERR_BAD_SHAPE, "bn_train_small_bwd: operands must be 16-byte aligned");
     static const int wide_b = MSPL_TUNE_INT("MSPL_BN_SMALL_WIDE", 2048);
     const int nt_b = (int64_t)N * ((HW & 3) == 0 ? HW / 4 : HW) >= wide_b ? 1024 : 256;
-    hipLaunchKernelGGL(bn_train_small_bwd_kernel, dim3((unsigned)C), dim3(nt_b), 0, (hipStream_t)stream, z, residual, gy, scale, shift, alpha,
-                       gamma, mean, invstd, N, C, HW, (float)(1.0 / ((double)N * (double)HW)), accumulate, gz, gres, ggamma, gbeta, galpha);
+    if ((int64_t)N * HW <= BN_FEW_VALUES)  // one or two values per channel: the statistics path in double
+        hipLaunchKernelGGL(bn_train_few_bwd_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, z, residual, gy, scale, shift, alpha,
+                           gamma, mean, N, C, HW, eps, accumulate, gz, gres, ggamma, gbeta, galpha);
+    else
+        hipLaunchKernelGGL(bn_train_small_bwd_kernel, dim3((unsigned)C), dim3(nt_b), 0, (hipStream_t)stream, z, residual, gy, scale, shift, alpha,
+                           gamma, mean, invstd, N, C, HW, (float)(1.0 / ((double)N * (double)HW)), accumulate, gz, gres, ggamma, gbeta, galpha);
     MSPL_CHECK_LAUNCH("bn_train_small_bwd");
     return MSPL_OK;
 }
