@@ -80,7 +80,9 @@ typedef struct {
 
 const char* mspl_version(void);
 /* ABI revision of this library; it changes whenever a struct layout or a signature in this header does.  5 = this header
- * (mspl_bn_train_small_bwd takes eps; 4: mspl_adam_step takes its betas as doubles). */
+ * (mspl_bn_train_small_bwd takes eps; 4: mspl_adam_step takes its betas as doubles).  The one place the number is written:
+ * mspl_abi_version() returns it, the epilogue check prints it, and the Python binding compares the two at import. */
+#define MSPL_ABI_VERSION 5
 int mspl_abi_version(void);
 /* Copies the calling thread's last error text (NUL-terminated) into buf; returns its length. */
 size_t mspl_last_error(char* buf, size_t cap);

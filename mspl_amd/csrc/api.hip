@@ -18,7 +18,7 @@ void set_error(const char* fmt, ...) {
 
 extern "C" const char* mspl_version(void) { return "mspl_hip 0.3 (gfx950)"; }
 
-extern "C" int mspl_abi_version(void) { return 5; }
+extern "C" int mspl_abi_version(void) { return MSPL_ABI_VERSION; }
 
 extern "C" size_t mspl_last_error(char* buf, size_t cap) {
     const size_t n = strlen(mspl::g_err);

@@ -131,7 +131,7 @@ static inline int check_epi(const mspl_epilogue_t* ep, int C, const char* who, b
     if (!ep) return MSPL_OK;
     MSPL_REQUIRE(ep->struct_size == sizeof(mspl_epilogue_t), MSPL_ERR_BAD_SHAPE,
                  "%s: epilogue struct size %u, this library expects %zu (caller built against another mspl_hip.h: ABI %d)", who,
-                 ep->struct_size, sizeof(mspl_epilogue_t), 3);
+                 ep->struct_size, sizeof(mspl_epilogue_t), MSPL_ABI_VERSION);
     MSPL_REQUIRE(!ep->raw_out || (raw_ok && (ep->out_ctot == 0 || (ep->out_ctot == C && ep->out_coff == 0))), MSPL_ERR_UNSUPPORTED,
                  "%s: raw_out is for un-sliced convolution outputs only", who);
     if (ep->out_ctot > 0) {

@@ -32,9 +32,137 @@ def test_every_declared_symbol_is_exported():
     lib = ctypes.CDLL(_native.LIB_PATH)
     for name in sorted(declared):
         assert hasattr(lib, name), 'include/mspl_hip.h declares %s but the library does not export it' % name
-    # and the Python binding table covers every compute entry point
-    assert set(_native.SIGNATURES) == declared - {'mspl_version', 'mspl_last_error'}
+    # and the Python binding, read from the same header, covers every one of them (mspl_version and mspl_last_error included)
+    assert set(_native.SIGNATURES) == declared == set(_native.RESTYPES)
     assert 'gfx950' in _native.version()
+
+
+# Every construct the real header uses, in a few lines: block comments that hold parentheses, semicolons and calls; a prototype over
+# five lines; (void); an array parameter; pointers to pointers; `1u`; a struct with a tag name and two names on one line.
+SYNTHETIC_HEADER = """
+/* mspl_hip.h -- calls mspl_alpha(1, 2); inside a comment (with parentheses; and semicolons)
+ * int mspl_alpha(int32_t not_this_one); */
+#ifndef MSPL_HIP_H
+#define MSPL_HIP_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef enum { MSPL_OK = 0, MSPL_ERR_BAD_SHAPE = -1,   /* non-positive (or inconsistent) dimensions; */
+               MSPL_ERR_HIP = -4 } mspl_status;
+typedef struct {
+    const float* scale;     /* (C) */
+    int32_t out_ctot;
+    float* raw_out;
+    uint32_t struct_size;   /* sizeof(mspl_epilogue_t) */
+} mspl_epilogue_t;
+#define MSPL_LAUNCH_THROUGHPUT 1u
+#define MSPL_FILTER_BILINEAR 2
+#define MSPL_ABI_VERSION 5
+const char* mspl_version(void);
+size_t mspl_last_error(char* buf, size_t cap);
+/* see mspl_beta() */
+int mspl_alpha(const float* x, const int32_t dil[4], int32_t stride,
+               const mspl_epilogue_t* ep,
+               const float* const* gy,
+               float* const* gw, const char* const* paths,
+               void* stream);
+typedef struct mspl_train_rec {
+    const int32_t* scale_x;
+    int32_t sh, sw;               /* size after RandomScale (= Hs, Ws) */
+} mspl_train_rec_t;
+int64_t mspl_beta(const mspl_train_rec_t* recs, unsigned long long* hist, const uint8_t* const* src, double M, float eps,
+                  uint32_t flags, int64_t n);
+void* mspl_gamma(int workers);
+#ifdef __cplusplus
+}
+#endif
+#endif /* MSPL_HIP_H */
+"""
+
+
+def test_header_parser_on_every_construct_of_the_header():
+    from mspl_amd._header import parse
+    c = ctypes
+    sig, res, structs, const = parse(SYNTHETIC_HEADER)
+    ep, rec = structs['mspl_epilogue_t'], structs['mspl_train_rec_t']
+    assert (ep.__name__, rec.__name__) == ('Epilogue', 'TrainRec')
+    assert ep._fields_ == [('scale', c.c_void_p), ('out_ctot', c.c_int32), ('raw_out', c.c_void_p), ('struct_size', c.c_uint32)]
+    assert rec._fields_ == [('scale_x', c.c_void_p), ('sh', c.c_int32), ('sw', c.c_int32)]
+    assert sig == {
+        'mspl_version': [],
+        'mspl_last_error': [c.c_char_p, c.c_size_t],
+        'mspl_alpha': [c.c_void_p, c.c_void_p, c.c_int32, c.POINTER(ep), c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+                       c.POINTER(c.c_char_p), c.c_void_p],
+        'mspl_beta': [c.c_void_p, c.c_void_p, c.POINTER(c.c_void_p), c.c_double, c.c_float, c.c_uint32, c.c_int64],
+        'mspl_gamma': [c.c_int32],
+    }
+    assert res == {'mspl_version': c.c_char_p, 'mspl_last_error': c.c_size_t, 'mspl_alpha': c.c_int32, 'mspl_beta': c.c_int64,
+                   'mspl_gamma': c.c_void_p}
+    assert const == {'OK': 0, 'ERR_BAD_SHAPE': -1, 'ERR_HIP': -4, 'LAUNCH_THROUGHPUT': 1, 'FILTER_BILINEAR': 2, 'ABI_VERSION': 5}
+
+
+@pytest.mark.parametrize('extra, says', [
+    ('int mspl_delta(int32_t n, long double x);', r'mspl_delta.*long double x'),                    # a type without a mapping
+    ('half_t mspl_delta(int32_t n);', r'mspl_delta.*half_t'),                                       # ... as a return type
+    ('int mspl_delta(const half_t* x);', r'mspl_delta.*half_t'),                                    # ... behind a pointer
+    ('int mspl_delta(float*** x);', r'mspl_delta.*float'),
+    ('int mspl_delta(int32_t (*callback)(int32_t), void* stream);', r'unmatched: mspl_delta'),      # a prototype the pattern misses
+    ('int mspl_delta(int32_t n) __attribute__((cold));', r'unmatched: mspl_delta'),
+    ('typedef enum { MSPL_ONE = 1, MSPL_TWO } mspl_two_t;', r'mspl_two_t.*explicit'),               # a value it would have to count
+    ('typedef struct { half_t h; } mspl_half_t;', r'mspl_half_t.*half_t'),
+])
+def test_header_parser_raises_on_what_it_does_not_understand(extra, says):
+    from mspl_amd._header import parse
+    with pytest.raises(ImportError, match=says):
+        parse(SYNTHETIC_HEADER.replace('void* mspl_gamma(int workers);', 'void* mspl_gamma(int workers);\n' + extra))
+
+
+def test_binding_spot_checks_against_the_real_header():
+    """A sample of the signatures that are easiest to get wrong by hand; not a second copy of the table."""
+    c = ctypes
+    sig, res = _native.SIGNATURES, _native.RESTYPES
+    p, pp, i32, f32 = c.c_void_p, c.POINTER(c.c_void_p), c.c_int32, c.c_float
+    assert sig['mspl_adam_step'] == [p, p, p, p, c.c_int64, f32, c.c_double, c.c_double, f32, f32, i32, p]
+    assert sig['mspl_conv1x1_wgrad_batch'] == [pp] * 4 + [p] * 5 + [i32, p]
+    assert sig['mspl_png_writer_submit'] == [p, p, i32, i32, i32, c.POINTER(c.c_char_p), p]
+    assert res['mspl_png_writer_submit'] is c.c_int64
+    assert sig['mspl_png_writer_create'] == [i32, i32] and res['mspl_png_writer_create'] is p
+    assert sig['mspl_bn_batch_stats_bwd_coeffs'] == [p] * 6 + [i32, c.c_double, i32] + [p] * 4 + [p]
+    assert sig['mspl_last_error'] == [c.c_char_p, c.c_size_t] and res['mspl_last_error'] is c.c_size_t
+    assert sig['mspl_version'] == [] and res['mspl_version'] is c.c_char_p
+    assert sig['mspl_conv1x1_fwd'] == [p, p] + [i32] * 5 + [_native._EP, p, p] and res['mspl_conv1x1_fwd'] is c.c_int
+    assert _native._EP is c.POINTER(_native.Epilogue)
+    assert res['mspl_bn_fused_workspace_bytes'] is c.c_int64 and res['mspl_nid_workspace_floats'] is c.c_int64      # size queries
+    assert (_native.FILTER_LANCZOS, _native.FILTER_BILINEAR, _native.ERR_UNSUPPORTED) == (1, 2, -2)
+    assert (_native.LAUNCH_THROUGHPUT, _native.LAUNCH_K2_STREAM_OFF, _native.LAUNCH_K2_STREAM_FORCE) == (1, 2, 4)
+    assert [_native.WGRAD_1X1_MFMA, _native.WGRAD_1X1_LDS, _native.WGRAD_STEM_S2_STRIP, _native.WGRAD_STEM_COB4, _native.WGRAD_STRIP,
+            _native.WGRAD_G3X3, _native.WGRAD_GENERIC] == list(range(1, 8))
+
+
+def test_structs_keep_their_layout():
+    c = ctypes
+    ep, rec = _native.Epilogue, _native.TrainRec
+    assert ep._fields_ == [(n, c.c_void_p) for n in ('scale', 'shift', 'alpha', 'pre_add', 'residual', 'reinf_r', 'reinf_w', 'gate')] + \
+        [('out_ctot', c.c_int32), ('out_coff', c.c_int32), ('raw_out', c.c_void_p), ('struct_size', c.c_uint32), ('flags', c.c_uint32)]
+    assert (ep.struct_size.offset, c.sizeof(ep)) == (80, 88)
+    assert rec._fields_ == [(n, c.c_void_p) for n in ('scale_x', 'scale_y', 'dscale_x', 'dscale_y', 'out_x', 'out_y', 'near_x', 'near_y',
+                                                      'near_out_x', 'near_out_y')] + \
+        [(n, c.c_int32) for n in ('sh', 'sw', 'pad_h', 'pad_w', 'crop_i', 'crop_j', 'flip', 'reserved')]
+    assert c.sizeof(rec) == 112
+
+
+def test_every_loaded_function_is_typed_from_the_header():
+    for name, argtypes in _native.SIGNATURES.items():
+        fn = getattr(_native.lib, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is _native.RESTYPES[name], name
+    # one revision number: the header's macro is what the library returns and what its epilogue check prints (that check comes
+    # before any launch and reads none of the tensors: host buffers stand in for them here)
+    assert _native.lib.mspl_abi_version() == _native.ABI_VERSION
+    ep = _native.Epilogue(struct_size=ctypes.sizeof(_native.Epilogue) - 8)
+    buf = ctypes.create_string_buffer(64)
+    assert _native.lib.mspl_conv1x1_fwd(buf, buf, 1, 8, 8, 1, 16, ctypes.byref(ep), buf, None) == _native.ERR_BAD_SHAPE
+    assert _native.last_error().endswith('ABI %d)' % _native.ABI_VERSION)
 
 
 @pytest.mark.parametrize('cfg', sorted(KEYS))
