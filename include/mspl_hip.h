@@ -322,6 +322,21 @@ int mspl_pyrpool_branch_bwd_fits(int32_t N, int32_t P, int32_t h, int32_t w, int
 int mspl_pyrpool_branch_bwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs,
                             const int32_t* ws, const float* const* stage_w, const float* const* gt, float* const* gw,
                             const float* add0, const float* add1, float* gx, void* stream);
+/* The form mspl_pyrpool_branch_bwd takes for these shapes. */
+typedef enum {
+    MSPL_PYR_BRANCH_BWD_UNSUPPORTED = 0,   /* the launcher returns MSPL_ERR_UNSUPPORTED (_fits: 0) */
+    MSPL_PYR_BRANCH_BWD_STREAM3 = 1,       /* every branch in one streaming launch: [up, up, same], [up, same], [up, up] or [up] */
+    MSPL_PYR_BRANCH_BWD_STREAM = 2,        /* one streaming launch per branch: the first overwrites gx, the others accumulate */
+    MSPL_PYR_BRANCH_BWD_TILE = 3           /* LDS tiles of 16 rows x 32 columns, every branch in one launch */
+} mspl_pyr_branch_bwd_form_t;
+/* What the launcher above decides, from the same host function it calls itself (no device call, no state).  aligned8: whether x,
+ * gx, add0, add1 and every gt[i] are 8-byte aligned, which the streaming forms require.  *form: an mspl_pyr_branch_bwd_form_t.
+ * Streaming forms: *ncb column blocks of 124 columns, *nseg row segments of *seg rows, taps[i] (three entries) = 3 or 5, the
+ * width of branch i's stencil (0 past nb).  Tile form: *tiles_x, *tiles_y tiles per plane.  What does not apply is 0; every output
+ * but form may be NULL. */
+int mspl_pyrpool_branch_bwd_plan(int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs, const int32_t* ws,
+                                 int32_t aligned8, int32_t* form, int32_t* ncb, int32_t* nseg, int32_t* seg, int32_t* taps,
+                                 int32_t* tiles_x, int32_t* tiles_y);
 
 /* K8+K9  label epilogue: bilinear(align_corners) upsample of both heads to (H,W), o = main + 0.5*aux,
  *     class = first-max argmax_c o (== np.argmax of softmax2d(o) up to exp() rounding ties), optional
@@ -452,6 +467,26 @@ int mspl_bilinear_bwd(const float* gy, int32_t N, int32_t C, int32_t Hi, int32_t
                       float* gx, void* stream);
 int mspl_adaptive_avgpool_bwd(const float* gy, int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                               float* gx, void* stream);
+/* The kernel forms behind mspl_bilinear_bwd and mspl_avgpool3x3s2_bwd. */
+typedef enum {
+    MSPL_BILINEAR_BWD_GENERIC8 = 1,   /* one thread per input pixel, at most 8 candidate columns kept in registers */
+    MSPL_BILINEAR_BWD_GENERIC12 = 2,  /* the same with 12 (more than that: a loop over the candidates) */
+    MSPL_BILINEAR_BWD_TILE8 = 3,      /* separable LDS tiles of 8 x 64 input pixels, row and column windows <= 8 */
+    MSPL_BILINEAR_BWD_TILE12 = 4,     /* tiles of 4 x 64, windows <= 12 */
+    MSPL_BILINEAR_BWD_WAVE = 5,       /* column windows > 12: a wave per input pixel */
+    MSPL_BILINEAR_BWD_ROWS = 6        /* column windows > 12 and Wo <= 8192: a workgroup per input row */
+} mspl_bilinear_bwd_form_t;
+typedef enum {
+    MSPL_AVGPOOL_BWD_VEC = 1,         /* H even, W % 8 == 0, 16-byte aligned operands: 16-byte strips */
+    MSPL_AVGPOOL_BWD_PLAIN = 2        /* one thread per input pixel */
+} mspl_avgpool_bwd_form_t;
+/* What the two launchers decide for a shape, each from the same host function the launcher calls itself (no device call, no
+ * state).  *form: an mspl_bilinear_bwd_form_t / mspl_avgpool_bwd_form_t.  Tile forms: *tiles_x, *tiles_y workgroups per plane
+ * and *FH x *FW, the largest window of output-gradient rows / columns one of them stages; 0 for the other forms; each may be
+ * NULL.  aligned / aligned16: whether gy and gx are 16-byte aligned (no bilinear form depends on it today). */
+int mspl_bilinear_bwd_plan(int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t aligned, int32_t* form,
+                           int32_t* tiles_x, int32_t* tiles_y, int32_t* FH, int32_t* FW);
+int mspl_avgpool3x3s2_bwd_plan(int32_t N, int32_t C, int32_t H, int32_t W, int32_t aligned16, int32_t* form);
 
 /* out[i] = sum_p a[i,p] * b[i,p] over `planes` planes of HW elements (b NULL: plain sum).  Gate / GAP gradients. */
 int mspl_plane_dot(const float* a, const float* b, int32_t planes, int32_t HW, float* out, void* stream);

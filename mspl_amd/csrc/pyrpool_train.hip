@@ -685,33 +685,50 @@ __global__ __launch_bounds__(256) void pyr_branch_bwd_stream_kernel(const float*
     }
 }
 
-// 0 = launched, 1 = shape not covered by the streaming form, < 0 error
-static int pyr_branch_bwd_stream_try(const float* x, const float* gt, const float* wst, const float* add0, const float* add1, int N,
-                                     int P, int h, int w, int hs, int ws, int accumulate, float* gx, float* gw, hipStream_t stream,
-                                     bool dry) {
+// How the streaming forms cut a plane: column blocks of SB_CBW columns, row segments of at most SB_SEGMAX rows (shorter while the
+// grid would not fill the device).  false: more waves than a grid holds.
+constexpr int SB_CBW = 124;
+struct SbSplit { int ncb, nseg, seg; };
+static bool sb_split(int N, int P, int h, int w, SbSplit& sp) {
+    sp.ncb = ceil_div(w, SB_CBW);
+    int seg = std::min(h, SB_SEGMAX);
+    while (seg > 8 && (int64_t)N * P * sp.ncb * ceil_div(h, seg) < 2048) --seg;
+    seg = ceil_div(h, ceil_div(h, seg));
+    sp.seg = seg;
+    sp.nseg = ceil_div(h, seg);
+    return (int64_t)N * P * sp.ncb * sp.nseg < (1ll << 31);
+}
+
+// the shapes the one-branch streaming form covers (operand alignment aside); taps: 3 or 5
+static bool pyr_branch_bwd_stream_shape(int N, int P, int h, int w, int hs, int ws, int& taps, SbSplit& sp) {
     static const int off = (MSPL_TUNE_INT("MSPL_PYR_BWD_STREAM", 1) == 0);
-    if (off || (w & 1) || ((int64_t)N * P) % 4 != 0 || hs < h || ws < w || h < 2 || w < 2) return 1;
-    if (!dry && ((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1)) & 7)) return 1;
+    if (off || (w & 1) || ((int64_t)N * P) % 4 != 0 || hs < h || ws < w || h < 2 || w < 2) return false;
     // (a branch of the map's own size is the plain 3x3: its coefficient tables have one unit entry inside the 3-tap band)
     const int Rr = (hs == h && ws == w) ? 1 : std::max(p3_stencil_radius(h, hs), p3_stencil_radius(w, ws));
-    if (Rr > 2) return 1;
-    if (dry) return 0;
+    if (Rr > 2) return false;
+    taps = Rr <= 1 ? 3 : 5;
+    return sb_split(N, P, h, w, sp);
+}
+
+// 0 = launched, 1 = shape not covered by the streaming form, < 0 error
+static int pyr_branch_bwd_stream_try(const float* x, const float* gt, const float* wst, const float* add0, const float* add1, int N,
+                                     int P, int h, int w, int hs, int ws, int accumulate, float* gx, float* gw, hipStream_t stream) {
+    int taps;
+    SbSplit sp;
+    if (!pyr_branch_bwd_stream_shape(N, P, h, w, hs, ws, taps, sp)) return 1;
+    if ((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1)) & 7) return 1;
     SbGeom g;
     memset(&g, 0, sizeof(g));
     g.N = N; g.P = P; g.h = h; g.w = w; g.hs = hs; g.ws = ws;
     g.sh = bilinear_scale(h, hs); g.sw = bilinear_scale(w, ws);
-    g.CBW = 124;
-    g.ncb = ceil_div(w, g.CBW);
-    int seg = std::min(h, SB_SEGMAX);
-    while (seg > 8 && (int64_t)N * P * g.ncb * ceil_div(h, seg) < 2048) --seg;
-    seg = ceil_div(h, ceil_div(h, seg));
-    g.SEG = seg;
-    g.nseg = ceil_div(h, seg);
+    g.CBW = SB_CBW;
+    g.ncb = sp.ncb;
+    g.SEG = sp.seg;
+    g.nseg = sp.nseg;
     g.accumulate = accumulate;
     const int64_t waves = (int64_t)N * P * g.ncb * g.nseg;
-    if (waves >= (1ll << 31)) return 1;
     const dim3 grid((unsigned)(waves / 4)), blk(256);
-    if (Rr <= 1) hipLaunchKernelGGL(pyr_branch_bwd_stream_kernel<3>, grid, blk, 0, stream, x, gt, wst, add0, add1, g, gx, gw);
+    if (taps == 3) hipLaunchKernelGGL(pyr_branch_bwd_stream_kernel<3>, grid, blk, 0, stream, x, gt, wst, add0, add1, g, gx, gw);
     else hipLaunchKernelGGL(pyr_branch_bwd_stream_kernel<5>, grid, blk, 0, stream, x, gt, wst, add0, add1, g, gx, gw);
     MSPL_CHECK_LAUNCH("pyrpool_branch_bwd(streaming form)");
     return 0;
@@ -929,24 +946,33 @@ __global__ __launch_bounds__(256) void pyr_branch_bwd_stream3_kernel(const float
     if (SAME) flush(dwc, gw2);
 }
 
+// the shapes the all-branches streaming form covers (operand alignment aside): [up, up, same], [up, same], [up, up] or [up]
+static bool pyr_branch_bwd_stream3_shape(int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws, int (&taps)[2],
+                                         bool& same, int& nup, SbSplit& sp) {
+    static const int off = (MSPL_TUNE_INT("MSPL_PYR_BWD_STREAM3", 1) == 0);
+    if (off || (w & 1) || w < 2 || h < 2 || ((int64_t)N * P) % 4 != 0 || nb < 1 || nb > 3) return false;
+    same = hs[nb - 1] == h && ws[nb - 1] == w;
+    nup = nb - (same ? 1 : 0);
+    if (nup < 1 || nup > 2) return false;
+    taps[0] = taps[1] = 3;
+    for (int i = 0; i < nup; ++i) {
+        if (hs[i] < h || ws[i] < w || (hs[i] == h && ws[i] == w)) return false;
+        const int Rr = std::max(p3_stencil_radius(h, hs[i]), p3_stencil_radius(w, ws[i]));
+        if (Rr > 2) return false;
+        taps[i] = Rr <= 1 ? 3 : 5;
+    }
+    return sb_split(N, P, h, w, sp);
+}
+
 // the standard pattern [up, up, same] (or [up, same] / [up, up] / [up]) in one launch; 0 = launched, 1 = not covered
 static int pyr_branch_bwd_stream3_try(const float* x, int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws,
                                       const float* const* stage_w, const float* const* gt, float* const* gw, const float* add0,
-                                      const float* add1, float* gx, hipStream_t stream, bool dry) {
-    static const int off = (MSPL_TUNE_INT("MSPL_PYR_BWD_STREAM3", 1) == 0);
-    if (off || (w & 1) || w < 2 || h < 2 || ((int64_t)N * P) % 4 != 0 || nb < 1 || nb > 3) return 1;
-    const bool same = hs[nb - 1] == h && ws[nb - 1] == w;
-    const int nup = nb - (same ? 1 : 0);
-    if (nup < 1 || nup > 2) return 1;
-    int taps[2] = {3, 3};
-    for (int i = 0; i < nup; ++i) {
-        if (hs[i] < h || ws[i] < w || (hs[i] == h && ws[i] == w)) return 1;
-        const int Rr = std::max(p3_stencil_radius(h, hs[i]), p3_stencil_radius(w, ws[i]));
-        if (Rr > 2) return 1;
-        taps[i] = Rr <= 1 ? 3 : 5;
-    }
-    if (!dry && ((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1) | ((uintptr_t)x)) & 7)) return 1;
-    if (dry) return 0;
+                                      const float* add1, float* gx, hipStream_t stream) {
+    int taps[2], nup;
+    bool same;
+    SbSplit sp;
+    if (!pyr_branch_bwd_stream3_shape(N, P, h, w, nb, hs, ws, taps, same, nup, sp)) return 1;
+    if ((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1) | ((uintptr_t)x)) & 7) return 1;
     for (int i = 0; i < nb; ++i)
         if ((((uintptr_t)gt[i]) & 7)) return 1;
     SbGeom g;
@@ -955,15 +981,11 @@ static int pyr_branch_bwd_stream3_try(const float* x, int N, int P, int h, int w
     g.sh = bilinear_scale(h, hs[0]); g.sw = bilinear_scale(w, ws[0]);
     const int hs1 = nup > 1 ? hs[1] : hs[0], ws1 = nup > 1 ? ws[1] : ws[0];
     const float sh1 = bilinear_scale(h, hs1), sw1 = bilinear_scale(w, ws1);
-    g.CBW = 124;
-    g.ncb = ceil_div(w, g.CBW);
-    int seg = std::min(h, SB_SEGMAX);
-    while (seg > 8 && (int64_t)N * P * g.ncb * ceil_div(h, seg) < 2048) --seg;
-    seg = ceil_div(h, ceil_div(h, seg));
-    g.SEG = seg;
-    g.nseg = ceil_div(h, seg);
+    g.CBW = SB_CBW;
+    g.ncb = sp.ncb;
+    g.SEG = sp.seg;
+    g.nseg = sp.nseg;
     const int64_t waves = (int64_t)N * P * g.ncb * g.nseg;
-    if (waves >= (1ll << 31)) return 1;
     const dim3 grid((unsigned)(waves / 4)), blk(256);
     const float* g1 = nup > 1 ? gt[1] : gt[0];
     const float* g2 = same ? gt[nb - 1] : gt[0];
@@ -1067,17 +1089,78 @@ static size_t ub_plan(int N, int P, int h, int w, int nb, const int32_t* hs, con
     return (size_t)off * sizeof(float);
 }
 
+// Which form mspl_pyrpool_branch_bwd takes for these shapes and how it cuts the planes: the ONE place where that is decided (the
+// launcher below switches on the result; _fits and mspl_pyrpool_branch_bwd_plan hand it to callers and tests).
+// al_out: gx, add0 and add1 are 8-byte aligned (both streaming forms store float2); al_in: x and every gt[i] are (the all-branches
+// form reads them as float2).
+struct BranchBwdPlan {
+    int form;                // mspl_pyr_branch_bwd_form_t
+    int ncb, nseg, seg;      // streaming forms: column blocks, row segments, rows per segment; else 0
+    int taps[3];             // streaming forms: 3 or 5 per branch; else 0
+    int tiles_x, tiles_y;    // tile form; else 0
+    size_t lds;              // tile form
+    UbGeom ub;               // tile form
+};
+
+static void pyr_branch_bwd_plan(int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws, bool al_out, bool al_in,
+                                BranchBwdPlan& p) {
+    memset(&p, 0, sizeof(p));
+    p.form = MSPL_PYR_BRANCH_BWD_UNSUPPORTED;
+    if (N <= 0 || P <= 0 || nb < 1 || nb > UB_MAXB) return;
+    SbSplit sp;
+    {   // every branch in one walk (the standard [up, up, same] pattern)
+        int taps[2], nup;
+        bool same;
+        if (al_out && al_in && pyr_branch_bwd_stream3_shape(N, P, h, w, nb, hs, ws, taps, same, nup, sp)) {
+            p.form = MSPL_PYR_BRANCH_BWD_STREAM3;
+            p.ncb = sp.ncb; p.nseg = sp.nseg; p.seg = sp.seg;
+            for (int i = 0; i < nup; ++i) p.taps[i] = taps[i];
+            if (same) p.taps[nb - 1] = 3;
+            return;
+        }
+    }
+    {   // streaming form: one launch per branch
+        bool all_stream = al_out;
+        int taps[UB_MAXB] = {0, 0, 0};
+        for (int i = 0; i < nb; ++i) all_stream = all_stream && pyr_branch_bwd_stream_shape(N, P, h, w, hs[i], ws[i], taps[i], sp);
+        if (all_stream) {
+            p.form = MSPL_PYR_BRANCH_BWD_STREAM;
+            p.ncb = sp.ncb; p.nseg = sp.nseg; p.seg = sp.seg;
+            for (int i = 0; i < nb; ++i) p.taps[i] = taps[i];
+            return;
+        }
+    }
+    p.lds = ub_plan(N, P, h, w, nb, hs, ws, p.ub);
+    if (p.lds > 0 && p.lds <= 64 * 1024 && (int64_t)N * P * p.ub.tiles_y < (1ll << 31)) {
+        p.form = MSPL_PYR_BRANCH_BWD_TILE;
+        p.tiles_x = p.ub.tiles_x; p.tiles_y = p.ub.tiles_y;
+    }
+}
+
+extern "C" int mspl_pyrpool_branch_bwd_plan(int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs,
+                                            const int32_t* ws, int32_t aligned8, int32_t* form, int32_t* ncb, int32_t* nseg,
+                                            int32_t* seg, int32_t* taps, int32_t* tiles_x, int32_t* tiles_y) {
+    MSPL_REQUIRE(hs && ws && form, MSPL_ERR_NULL_POINTER, "pyrpool_branch_bwd_plan: null pointer");
+    BranchBwdPlan p;
+    pyr_branch_bwd_plan(N, P, h, w, nb, hs, ws, aligned8 != 0, aligned8 != 0, p);
+    *form = p.form;
+    if (ncb) *ncb = p.ncb;
+    if (nseg) *nseg = p.nseg;
+    if (seg) *seg = p.seg;
+    if (taps) for (int i = 0; i < UB_MAXB; ++i) taps[i] = p.taps[i];
+    if (tiles_x) *tiles_x = p.tiles_x;
+    if (tiles_y) *tiles_y = p.tiles_y;
+    return MSPL_OK;
+}
+
 extern "C" int mspl_pyrpool_branch_bwd_fits(int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs,
                                             const int32_t* ws) {
     if (!hs || !ws || N <= 0 || P <= 0) return 0;
-    if (pyr_branch_bwd_stream3_try(nullptr, N, P, h, w, nb, hs, ws, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true) == 0) return 1;
-    bool all_stream = nb >= 1;
-    for (int i = 0; i < nb; ++i)
-        all_stream = all_stream && pyr_branch_bwd_stream_try(nullptr, nullptr, nullptr, nullptr, nullptr, N, P, h, w, hs[i], ws[i], 0, nullptr, nullptr, nullptr, true) == 0;
-    if (all_stream) return 1;
-    UbGeom g;
-    const size_t lds = ub_plan(N, P, h, w, nb, hs, ws, g);
-    return lds > 0 && lds <= 64 * 1024 && (int64_t)N * P * g.tiles_y < (1ll << 31);
+    // (operands that are not 8-byte aligned go to the tile form: what fits there is the question)
+    BranchBwdPlan p;
+    pyr_branch_bwd_plan(N, P, h, w, nb, hs, ws, true, true, p);
+    if (p.form != MSPL_PYR_BRANCH_BWD_UNSUPPORTED) return 1;
+    return 0;
 }
 
 extern "C" int mspl_pyrpool_branch_bwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs,
@@ -1087,39 +1170,37 @@ extern "C" int mspl_pyrpool_branch_bwd(const float* x, int32_t N, int32_t P, int
     MSPL_REQUIRE(N > 0 && P > 0 && h > 0 && w > 0, MSPL_ERR_BAD_SHAPE, "pyrpool_branch_bwd: bad shape N=%d P=%d %dx%d", N, P, h, w);
     MSPL_REQUIRE(nb >= 1 && nb <= UB_MAXB, MSPL_ERR_UNSUPPORTED, "pyrpool_branch_bwd: %d branches (1..%d)", nb, UB_MAXB);
     for (int i = 0; i < nb; ++i) MSPL_REQUIRE(stage_w[i] && gt[i] && gw[i], MSPL_ERR_NULL_POINTER, "pyrpool_branch_bwd: branch %d pointer", i);
-    {   // every branch in one walk (the standard [up, up, same] pattern)
-        const int rc = pyr_branch_bwd_stream3_try(x, N, P, h, w, nb, hs, ws, stage_w, gt, gw, add0, add1, gx, (hipStream_t)stream, false);
-        if (rc <= 0) return rc;
+    const bool al_out = ((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1)) & 7) == 0;
+    bool al_in = (((uintptr_t)x) & 7) == 0;
+    for (int i = 0; i < nb; ++i) al_in = al_in && (((uintptr_t)gt[i]) & 7) == 0;
+    BranchBwdPlan plan;
+    pyr_branch_bwd_plan(N, P, h, w, nb, hs, ws, al_out, al_in, plan);
+    switch (plan.form) {
+    case MSPL_PYR_BRANCH_BWD_STREAM3: {
+        const int rc = pyr_branch_bwd_stream3_try(x, N, P, h, w, nb, hs, ws, stage_w, gt, gw, add0, add1, gx, (hipStream_t)stream);
+        MSPL_REQUIRE(rc <= 0, MSPL_ERR_UNSUPPORTED, "pyrpool_branch_bwd: the all-branches streaming form refused shapes its plan accepted");
+        return rc;
     }
-    {   // streaming form: one launch per branch, the first one overwrites gx (and adds add0 / add1), the others accumulate
-        bool all_stream = true;
+    case MSPL_PYR_BRANCH_BWD_STREAM:      // one launch per branch, the first one overwrites gx (and adds add0 / add1), the others accumulate
         for (int i = 0; i < nb; ++i) {
-            MSPL_REQUIRE(stage_w[i] && gt[i] && gw[i], MSPL_ERR_NULL_POINTER, "pyrpool_branch_bwd: branch %d pointer", i);
-            all_stream = all_stream && pyr_branch_bwd_stream_try(x, gt[i], stage_w[i], add0, add1, N, P, h, w, hs[i], ws[i], 0, gx, gw[i], nullptr, true) == 0;
+            const int rc = pyr_branch_bwd_stream_try(x, gt[i], stage_w[i], i == 0 ? add0 : nullptr, i == 0 ? add1 : nullptr, N, P, h, w,
+                                                     hs[i], ws[i], i > 0, gx, gw[i], (hipStream_t)stream);
+            MSPL_REQUIRE(rc <= 0, MSPL_ERR_UNSUPPORTED, "pyrpool_branch_bwd: streaming form refused branch %d after accepting it", i);
+            if (rc < 0) return rc;
         }
-        all_stream = all_stream && !((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1)) & 7);
-        if (all_stream) {
-            for (int i = 0; i < nb; ++i) {
-                const int rc = pyr_branch_bwd_stream_try(x, gt[i], stage_w[i], i == 0 ? add0 : nullptr, i == 0 ? add1 : nullptr, N, P, h, w,
-                                                         hs[i], ws[i], i > 0, gx, gw[i], (hipStream_t)stream, false);
-                MSPL_REQUIRE(rc <= 0, MSPL_ERR_UNSUPPORTED, "pyrpool_branch_bwd: streaming form refused branch %d after accepting it", i);
-                if (rc < 0) return rc;
-            }
-            return MSPL_OK;
-        }
+        return MSPL_OK;
+    case MSPL_PYR_BRANCH_BWD_TILE:
+        break;
+    default:
+        MSPL_REQUIRE(plan.lds > 0 && plan.lds <= 64 * 1024, MSPL_ERR_UNSUPPORTED,
+                     "pyrpool_branch_bwd: %d branches on a %dx%d map are not covered (sizes must be in [1x, 3x], tile LDS %zu B)", nb, h, w, plan.lds);
+        MSPL_REQUIRE(false, MSPL_ERR_BAD_SHAPE, "pyrpool_branch_bwd: grid too large");
     }
-    UbGeom g;
-    const size_t lds = ub_plan(N, P, h, w, nb, hs, ws, g);
-    MSPL_REQUIRE(lds > 0 && lds <= 64 * 1024, MSPL_ERR_UNSUPPORTED,
-                 "pyrpool_branch_bwd: %d branches on a %dx%d map are not covered (sizes must be in [1x, 3x], tile LDS %zu B)", nb, h, w, lds);
-    for (int i = 0; i < nb; ++i) {
-        MSPL_REQUIRE(stage_w[i] && gt[i] && gw[i], MSPL_ERR_NULL_POINTER, "pyrpool_branch_bwd: branch %d pointer", i);
-        g.b[i].w = stage_w[i]; g.b[i].gt = gt[i]; g.b[i].gw = gw[i];
-    }
+    UbGeom& g = plan.ub;
+    for (int i = 0; i < nb; ++i) { g.b[i].w = stage_w[i]; g.b[i].gt = gt[i]; g.b[i].gw = gw[i]; }
     g.add0 = add0; g.add1 = add1;
     const int64_t blocks = (int64_t)N * P * g.tiles_y;
-    MSPL_REQUIRE(blocks < (1ll << 31), MSPL_ERR_BAD_SHAPE, "pyrpool_branch_bwd: grid too large");
-    hipLaunchKernelGGL(pyr_branch_bwd_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, x, g, gx);
+    hipLaunchKernelGGL(pyr_branch_bwd_kernel, dim3((unsigned)blocks), dim3(256), plan.lds, (hipStream_t)stream, x, g, gx);
     MSPL_CHECK_LAUNCH("pyrpool_branch_bwd");
     return MSPL_OK;
 }

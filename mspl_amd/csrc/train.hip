@@ -1499,13 +1499,31 @@ extern "C" int mspl_bn_prelu_bwd(const float* c, const float* pre_add, const flo
                                    bn_inv, stream);
 }
 
-static int rs_geom(const char* who, const float* gy, float* gx, int N, int C, int Hi, int Wi, int Ho, int Wo, RsG& g) {
-    MSPL_REQUIRE(gy && gx, MSPL_ERR_NULL_POINTER, "%s: null pointer", who);
-    MSPL_REQUIRE(N > 0 && C > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, MSPL_ERR_BAD_SHAPE, "%s: bad shape", who);
+static void rs_geom_fill(int N, int C, int Hi, int Wi, int Ho, int Wo, RsG& g) {
     g.N = N; g.C = C; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo;
     g.sh = bilinear_scale(Hi, Ho); g.sw = bilinear_scale(Wi, Wo);
     auto magic = [](int d) { return (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); };
     g.mHi = magic(Hi); g.mWi = magic(Wi); g.mHo = magic(Ho); g.mWo = magic(Wo);
+}
+
+static int rs_geom(const char* who, const float* gy, float* gx, int N, int C, int Hi, int Wi, int Ho, int Wo, RsG& g) {
+    MSPL_REQUIRE(gy && gx, MSPL_ERR_NULL_POINTER, "%s: null pointer", who);
+    MSPL_REQUIRE(N > 0 && C > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, MSPL_ERR_BAD_SHAPE, "%s: bad shape", who);
+    rs_geom_fill(N, C, Hi, Wi, Ho, Wo, g);
+    return MSPL_OK;
+}
+
+// Which kernel form mspl_avgpool3x3s2_bwd launches: decided here and nowhere else (the launcher switches on the result,
+// mspl_avgpool3x3s2_bwd_plan hands it to callers and tests).  aligned16: gy and gx are both 16-byte aligned.
+static int avgpool3x3s2_bwd_plan(int H, int W, bool aligned16) {
+    return ((H & 1) == 0 && (W & 7) == 0 && aligned16) ? MSPL_AVGPOOL_BWD_VEC : MSPL_AVGPOOL_BWD_PLAIN;      // whole 16-byte strips on both sides
+}
+
+extern "C" int mspl_avgpool3x3s2_bwd_plan(int32_t N, int32_t C, int32_t H, int32_t W, int32_t aligned16, int32_t* form) {
+    MSPL_REQUIRE(form, MSPL_ERR_NULL_POINTER, "avgpool3x3s2_bwd_plan: null pointer");
+    MSPL_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, MSPL_ERR_BAD_SHAPE, "avgpool3x3s2_bwd_plan: bad shape");
+    MSPL_REQUIRE((int64_t)H * W * W < (1ll << 32), MSPL_ERR_BAD_SHAPE, "avgpool3x3s2_bwd_plan: plane too large for 32-bit index arithmetic");
+    *form = avgpool3x3s2_bwd_plan(H, W, aligned16 != 0);
     return MSPL_OK;
 }
 
@@ -1515,7 +1533,7 @@ extern "C" int mspl_avgpool3x3s2_bwd(const float* gy, int32_t N, int32_t C, int3
     const int64_t total = (int64_t)N * C * H * W;
     MSPL_REQUIRE((int64_t)H * W * W < (1ll << 32), MSPL_ERR_BAD_SHAPE, "avgpool3x3s2_bwd: plane too large for 32-bit index arithmetic");
     const int planes = N * C, gyd = planes < 65535 ? planes : 65535;
-    if ((H & 1) == 0 && (W & 7) == 0 && ((((uintptr_t)gy) | ((uintptr_t)gx)) & 15) == 0) {      // whole 16-byte strips on both sides
+    if (avgpool3x3s2_bwd_plan(H, W, ((((uintptr_t)gy) | ((uintptr_t)gx)) & 15) == 0) == MSPL_AVGPOOL_BWD_VEC) {
         const int XS = g.Wo / 4;
         hipLaunchKernelGGL(avgpool3x3s2_bwd_vec_kernel, dim3((unsigned)ceil_div(g.Ho * XS, 256), (unsigned)gyd, (unsigned)ceil_div(planes, gyd)),
                            dim3(256), 0, (hipStream_t)stream, gy, g, XS, gx);
@@ -1528,28 +1546,27 @@ extern "C" int mspl_avgpool3x3s2_bwd(const float* gy, int32_t N, int32_t C, int3
     return MSPL_OK;
 }
 
-/* Gather form: gx is overwritten. */
-extern "C" int mspl_bilinear_bwd(const float* gy, int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
-                                 float* gx, void* stream) {
-    RsG g;
-    if (int rc = rs_geom("bilinear_bwd", gy, gx, N, C, Hi, Wi, Ho, Wo, g)) return rc;
+// Which kernel form mspl_bilinear_bwd launches for a shape, and the tile forms' grid and LDS extents: the ONE place where that is
+// decided (the launcher below switches on the result; mspl_bilinear_bwd_plan hands it to callers and tests).  No form depends on
+// the operands' alignment.
+struct BilinearBwdPlan {
+    int form;                // mspl_bilinear_bwd_form_t
+    int tiles_x, tiles_y;    // tile forms: workgroups per plane along x / y; else 0
+    int FH, FW;              // tile forms: staged output-gradient rows / columns; else 0
+    int FWS;                 // tile forms: LDS row stride
+    size_t lds;
+};
+
+static BilinearBwdPlan bilinear_bwd_plan(const RsG& g) {
+    BilinearBwdPlan p;
+    memset(&p, 0, sizeof(p));
+    const int N = g.N, C = g.C, Hi = g.Hi, Wi = g.Wi, Ho = g.Ho, Wo = g.Wo;
     const int64_t total = (int64_t)N * C * Hi * Wi;
     // candidate window per input pixel is 2/scale + 3 wide: beyond 12 columns a wave per input pixel is the better shape
     const bool wide = g.sw <= 0.f || 2.0f / g.sw + 3.0f > 12.0f;
     static const int rows_form = MSPL_TUNE_INT("MSPL_BILINEAR_BWD_ROWS", 1);
-    if (wide && rows_form && Wo <= 8192 && (int64_t)N * C * Hi < (1ll << 31)) {
-        hipLaunchKernelGGL(bilinear_bwd_rows_kernel, dim3((unsigned)((int64_t)N * C * Hi)), dim3(256), (size_t)Wo * sizeof(float),
-                           (hipStream_t)stream, gy, g, gx);
-        MSPL_CHECK_LAUNCH("bilinear_bwd(rows)");
-        return MSPL_OK;
-    }
-    if (wide && total * 64 < (1ll << 31) * 256ll) {
-        hipLaunchKernelGGL(bilinear_bwd_wave_kernel, dim3((unsigned)ceil_div64(total * 64, 256)), dim3(256), 0, (hipStream_t)stream, gy, g,
-                           gx, total);
-        MSPL_CHECK_LAUNCH("bilinear_bwd(wave)");
-        return MSPL_OK;
-    }
-    const int planes = N * C, gyd = planes < 65535 ? planes : 65535;
+    if (wide && rows_form && Wo <= 8192 && (int64_t)N * C * Hi < (1ll << 31)) { p.form = MSPL_BILINEAR_BWD_ROWS; return p; }
+    if (wide && total * 64 < (1ll << 31) * 256ll) { p.form = MSPL_BILINEAR_BWD_WAVE; return p; }
     static const int tile_form = MSPL_TUNE_INT("MSPL_BILINEAR_BWD_TILE", 1);
     if (tile_form && g.sh > 0.f && g.sw > 0.f) {
         // candidate windows (rows and columns) of at most 8 (x2) or 12 (x4): the tiled separable form
@@ -1572,19 +1589,70 @@ extern "C" int mspl_bilinear_bwd(const float* gy, int32_t N, int32_t C, int32_t 
             const int FWS = ((FW + maxc + 3) & ~3) | 4;            // row stride: staged columns + the candidates' over-read, not a multiple of 8 floats
             const size_t lds = ((size_t)FH * FWS + (size_t)(FH + maxc) * TLW + (size_t)maxc * TLW + (size_t)TLH * maxc + TLW + TLH) * sizeof(float);
             if (lds <= 64 * 1024 && (int64_t)tiles_x * tiles_y < (1ll << 31)) {
-                const dim3 tgrid((unsigned)(tiles_x * tiles_y), (unsigned)gyd, (unsigned)ceil_div(planes, gyd));
-                if (maxc == 8) hipLaunchKernelGGL((bilinear_bwd_tile_kernel<8, 8>), tgrid, dim3(256), lds, (hipStream_t)stream, gy, g, FH, FWS, tiles_x, gx);
-                else hipLaunchKernelGGL((bilinear_bwd_tile_kernel<12, 4>), tgrid, dim3(256), lds, (hipStream_t)stream, gy, g, FH, FWS, tiles_x, gx);
-                MSPL_CHECK_LAUNCH("bilinear_bwd(tiled)");
-                return MSPL_OK;
+                p.form = maxc == 8 ? MSPL_BILINEAR_BWD_TILE8 : MSPL_BILINEAR_BWD_TILE12;
+                p.tiles_x = tiles_x; p.tiles_y = tiles_y; p.FH = FH; p.FW = FW; p.FWS = FWS; p.lds = lds;
+                return p;
             }
         }
     }
+    // x2 up-sampling (the decoder, the heads): at most 7 candidate columns
+    p.form = (g.sw > 0.f && 2.0f / g.sw + 3.0f <= 8.0f) ? MSPL_BILINEAR_BWD_GENERIC8 : MSPL_BILINEAR_BWD_GENERIC12;
+    return p;
+}
+
+extern "C" int mspl_bilinear_bwd_plan(int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t aligned,
+                                      int32_t* form, int32_t* tiles_x, int32_t* tiles_y, int32_t* FH, int32_t* FW) {
+    (void)aligned;
+    MSPL_REQUIRE(form, MSPL_ERR_NULL_POINTER, "bilinear_bwd_plan: null pointer");
+    MSPL_REQUIRE(N > 0 && C > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, MSPL_ERR_BAD_SHAPE, "bilinear_bwd_plan: bad shape");
+    RsG g;
+    rs_geom_fill(N, C, Hi, Wi, Ho, Wo, g);
+    const BilinearBwdPlan p = bilinear_bwd_plan(g);
+    *form = p.form;
+    if (tiles_x) *tiles_x = p.tiles_x;
+    if (tiles_y) *tiles_y = p.tiles_y;
+    if (FH) *FH = p.FH;
+    if (FW) *FW = p.FW;
+    return MSPL_OK;
+}
+
+/* Gather form: gx is overwritten. */
+extern "C" int mspl_bilinear_bwd(const float* gy, int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                                 float* gx, void* stream) {
+    RsG g;
+    if (int rc = rs_geom("bilinear_bwd", gy, gx, N, C, Hi, Wi, Ho, Wo, g)) return rc;
+    const int64_t total = (int64_t)N * C * Hi * Wi;
+    const BilinearBwdPlan plan = bilinear_bwd_plan(g);
+    const int planes = N * C, gyd = planes < 65535 ? planes : 65535;
     const dim3 grid((unsigned)ceil_div(Hi * Wi, 256), (unsigned)gyd, (unsigned)ceil_div(planes, gyd));
-    if (g.sw > 0.f && 2.0f / g.sw + 3.0f <= 8.0f)          // x2 up-sampling (the decoder, the heads): at most 7 candidate columns
+    switch (plan.form) {
+    case MSPL_BILINEAR_BWD_ROWS:
+        hipLaunchKernelGGL(bilinear_bwd_rows_kernel, dim3((unsigned)((int64_t)N * C * Hi)), dim3(256), (size_t)Wo * sizeof(float),
+                           (hipStream_t)stream, gy, g, gx);
+        MSPL_CHECK_LAUNCH("bilinear_bwd(rows)");
+        return MSPL_OK;
+    case MSPL_BILINEAR_BWD_WAVE:
+        hipLaunchKernelGGL(bilinear_bwd_wave_kernel, dim3((unsigned)ceil_div64(total * 64, 256)), dim3(256), 0, (hipStream_t)stream, gy, g,
+                           gx, total);
+        MSPL_CHECK_LAUNCH("bilinear_bwd(wave)");
+        return MSPL_OK;
+    case MSPL_BILINEAR_BWD_TILE8:
+    case MSPL_BILINEAR_BWD_TILE12: {
+        const dim3 tgrid((unsigned)(plan.tiles_x * plan.tiles_y), (unsigned)gyd, (unsigned)ceil_div(planes, gyd));
+        if (plan.form == MSPL_BILINEAR_BWD_TILE8)
+            hipLaunchKernelGGL((bilinear_bwd_tile_kernel<8, 8>), tgrid, dim3(256), plan.lds, (hipStream_t)stream, gy, g, plan.FH, plan.FWS, plan.tiles_x, gx);
+        else
+            hipLaunchKernelGGL((bilinear_bwd_tile_kernel<12, 4>), tgrid, dim3(256), plan.lds, (hipStream_t)stream, gy, g, plan.FH, plan.FWS, plan.tiles_x, gx);
+        MSPL_CHECK_LAUNCH("bilinear_bwd(tiled)");
+        return MSPL_OK;
+    }
+    case MSPL_BILINEAR_BWD_GENERIC8:
         hipLaunchKernelGGL(bilinear_bwd_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, gy, g, gx, total);
-    else
+        break;
+    default:
         hipLaunchKernelGGL(bilinear_bwd_kernel<12>, grid, dim3(256), 0, (hipStream_t)stream, gy, g, gx, total);
+        break;
+    }
     MSPL_CHECK_LAUNCH("bilinear_bwd");
     return MSPL_OK;
 }

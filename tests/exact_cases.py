@@ -336,10 +336,56 @@ def ref_sums(cfg, p, dtype):
             'broadcast': bc, 'broadcast_acc': bc + p['pre'].to(dtype)}
 
 
+def make_pyr_merge(cfg):
+    """zcat and gy are drawn; mraw is the reference's own convolution result (exact on these data).  Unit-magnitude data and the
+    integer-scale subsets: merge_layer.2's parameter gradients are sums over whole planes of products of a nine-tap-per-branch sum."""
+    N, P, h, w, nb = cfg['shape']
+    v = VALS[1:3]
+    p = {'zcat': draw((N, nb * P, h, w), 6, v), 'gy': draw((N, P, h, w), 2, v), 'merge_w': draw((P, nb, 3, 3), 4, v)}
+    _bn_params(p, 'br_', nb * P, 10, cfg['mean_inv'], True)
+    _bn_params(p, 'm_', P, 20, cfg['mean_inv'], True)
+    if not cfg['m_alpha']:
+        del p['m_alpha']
+    p['mraw'] = merge_conv(p, cfg['shape'], torch.float64)
+    return p
+
+
+def _merge_forward(p, shape, dtype):
+    """merge_layer.0 (BatchNorm + PReLU over the concatenation), Shuffle, merge_layer.2's grouped 3x3 -> (m, leaves)."""
+    N, P, h, w, nb = shape
+    z, wm, bal = _leaf(p['zcat'], dtype), _leaf(p['merge_w'], dtype), _leaf(p['br_alpha'], dtype)
+    u, ba, bb = _bn(z, p, 'br_', dtype)
+    y = _prelu(u, bal, p).view(N, nb, P, h, w).transpose(1, 2).reshape(N, P * nb, h, w)
+    return F.conv2d(y, wm, None, 1, 1, 1, P), [z, ba, bb, bal, wm]
+
+
+def merge_conv(p, shape, dtype):
+    return _merge_forward(p, shape, dtype)[0].detach()
+
+
+def ref_pyr_merge(cfg, p, dtype):
+    """mspl_pyrpool_merge_bwd: out = [PReLU](BN(m)), m = conv3x3(Shuffle(PReLU(BN(zcat)))), cotangent gy.  The kernel is handed the kept
+    convolution result as data: mraw + (m - m.detach()) has mraw's value exactly and the convolution's derivative.  gt is
+    branch-major (nb, N, P, h, w)."""
+    N, P, h, w, nb = cfg['shape']
+    m, leaves = _merge_forward(p, cfg['shape'], dtype)
+    u, ma, mb = _bn(p['mraw'].to(dtype) + (m - m.detach()), p, 'm_', dtype)
+    leaves += [ma, mb]
+    if 'm_alpha' in p:
+        mal = _leaf(p['m_alpha'], dtype)
+        u = _prelu(u, mal, p)
+        leaves.append(mal)
+    g = dict(zip(['gt', 'g_br_scale', 'g_br_shift', 'g_br_alpha', 'g_merge_w', 'g_m_scale', 'g_m_shift', 'g_m_alpha'],
+                 _grad([(p['gy'].to(dtype), u)], leaves)))
+    g['gt'] = g['gt'].view(N, nb, P, h, w).transpose(0, 1).contiguous()
+    return g
+
+
 OPS = {'conv_wgrad': (make_conv_wgrad, ref_conv_wgrad), 'conv_dgrad': (make_conv_dgrad, ref_conv_dgrad),
        'eesp_dw': (make_eesp_dw, ref_eesp_dw), 'eesp_fused': (make_eesp_fused, ref_eesp_fused), 'hff_bn': (make_hff_bn, ref_hff_bn),
        'hff_sum': (make_hff_sum, ref_hff_sum), 'affine': (make_affine, ref_affine), 'down_tail': (make_down_tail, ref_down_tail),
-       'wgrad_batch': (make_wgrad_batch, ref_wgrad_batch), 'dense': (make_dense, ref_dense), 'sums': (make_sums, ref_sums)}
+       'wgrad_batch': (make_wgrad_batch, ref_wgrad_batch), 'dense': (make_dense, ref_dense), 'sums': (make_sums, ref_sums),
+       'pyr_merge': (make_pyr_merge, ref_pyr_merge)}
 
 # Q per output: 2^-Q is the finest grid an intermediate of that output lies on, in the kernel's or the reference's order.  With g, z,
 # c, x, w integers; scale, inv on 2^-1; alpha, mean, shift on 2^-2:
@@ -359,13 +405,17 @@ GRIDS = {
     # with the projection tail (coarse sets: scale, inv integers; alpha, shift, mean on 2^-1): u, gz, G, acc = sum w * G on 2^-1;
     # x = PReLU(u_p): 2^-2, so gw = sum G * x: 2^-3; acc * alpha_p [* c | * scale_p]: 2^-2; d gamma = (. - mean * .) * inv: one bit more
     # than its sums (gscale: 2^-2, gpscale: 2^-3); acc * u_p: 2^-2
+    # pyr_merge (coarse sets, unit data): u on 2^-1, y = PReLU(u) on 2^-2, m = sum w * y on 2^-2; g_m = gy [* alpha_m] * scale_m on 2^-1;
+    # gyi = sum w * g_m: 2^-1, * alpha_b: 2^-2 (gt, sum gz, sum gz * z); sum y * g_m: 2^-3; sum gyi * u: 2^-2; d gamma: one bit more than
+    # its sums; merge_layer.2: gz * m on 2^-3, sum gz on 2^-1, gy * (m * scale + shift) on 2^-2
+    'pyr_merge': {'gt': 2, 'g_merge_w': 3, 'g_br_scale': 3, 'g_br_shift': 2, 'g_br_alpha': 2, 'g_m_scale': 3, 'g_m_shift': 1, 'g_m_alpha': 2},
     'eesp_fused_tail': {'gx': 2, 'gw': 3, 'gscale': 2, 'gshift': 1, 'galpha': 1, 'gpscale': 3, 'gpshift': 2, 'gpalpha': 2},
 }
 
 
 def grid_q(case, name):
     key = 'eesp_fused_tail' if case.op == 'eesp_fused' and case.cfg['tail'] else case.op
-    return GRIDS[key][name.rstrip('0123456789')]
+    return GRIDS[key][name if case.op == 'pyr_merge' else name.rstrip('0123456789')]
 
 
 @functools.lru_cache(maxsize=None)
@@ -511,6 +561,13 @@ CASES += [_case('dense', 'x'.join(str(v) for v in s) + '-split%d' % sp, shape=s,
                         ((4, 32, 32, 40, 40, 3, 3), 1), ((4, 32, 32, 40, 40, 3, 3), 2), ((4, 32, 32, 40, 40, 3, 3), 5),
                         ((4, 32, 32, 40, 40, 3, 3), 0)]]
 CASES += [_case('sums', 'quads', shape=(6, 1028, 3)), _case('sums', 'small', shape=(3, 8, 8))]      # (planes, HW, tensors)
+
+# (N, P, h, w, nb): one tile; a one-row band and a one-column tile; three bands of three tiles; w % 4 != 0 (the scalar path); every nb
+for _shape in [(1, 4, 16, 64, 5), (1, 4, 17, 65, 5), (2, 3, 33, 130, 3), (1, 2, 9, 67, 2), (1, 1, 5, 6, 1), (1, 2, 17, 65, 4)]:
+    for _al in (1, 0):
+        for _mi in (0, 1):
+            CASES.append(_case('pyr_merge', '%dx%dx%dx%d-nb%d-alpha%d-mean%d' % (_shape + (_al, _mi)), shape=_shape, m_alpha=bool(_al),
+                               mean_inv=bool(_mi)))
 
 BY_ID = {c.id: c for c in CASES}
 assert len(BY_ID) == len(CASES)

@@ -174,9 +174,14 @@ def run_sums(cfg, p, lib, check):
     return o
 
 
+def run_pyr_merge(cfg, p, lib, check):
+    from tests.test_gpu_pyramid_grad import run_pyr_merge as run
+    return run(cfg['shape'], p, lib, check, pre=0.0)
+
+
 RUN = {'conv_wgrad': run_conv_wgrad, 'conv_dgrad': run_conv_dgrad, 'eesp_dw': run_eesp_dw, 'eesp_fused': run_eesp_fused, 'hff_bn': run_hff_bn,
        'hff_sum': run_hff_sum, 'affine': run_affine, 'down_tail': run_down_tail, 'wgrad_batch': run_wgrad_batch, 'dense': run_dense,
-       'sums': run_sums}
+       'sums': run_sums, 'pyr_merge': run_pyr_merge}
 
 
 def _where(case, name, idx):
@@ -186,6 +191,8 @@ def _where(case, name, idx):
         bands, rows = ec.fused_bands(cfg['shape'], cfg['dil'])
         return 'image %d channel %d band %d of %d (rows %d..%d), row %d' % (idx[0], idx[1], idx[2] // rows, bands, idx[2] // rows * rows,
                                                                             min(cfg['shape'][2], (idx[2] // rows + 1) * rows) - 1, idx[2])
+    if case.op == 'pyr_merge' and name == 'gt':
+        return 'branch %d image %d channel %d row %d (band %d) column %d (tile %d)' % (tuple(idx[:4]) + (idx[3] // 16, idx[4], idx[4] // 64))
     if case.op in ('hff_bn', 'hff_sum') and name == 'out':
         return 'branch %d image %d channel %d pixel %d of %d' % (tuple(idx) + (cfg['shape'][2],))
     return ''
