@@ -104,8 +104,8 @@ def barrier():
 
 
 class GradBucket:
-    """Flat fp32 bucket over the parameters that receive gradients -- the ONE implementation of the flat layout: FlatAdam and
-    FlatSGD (mspl_amd/training.py, supervised.py) build their buffers through it.
+    """Flat fp32 bucket over the parameters that receive gradients -- the ONE implementation of the flat layout:
+    steps.FlatOptimizer builds the buffers of FlatAdam (training.py) and FlatSGD (supervised.py) through it.
 
     Call after the first backward (which reveals the unused parameters, exactly the set torch.optim skips):
     `GradBucket(model.parameters())`.  The parameters' .grad tensors become views into one contiguous buffer `flat`, so

@@ -254,14 +254,12 @@ def patch_script(namespace, train=False):
 
 
 # ------------------------------------------------------------- train_seg_ue() (utilities/train_eval_seg.py:164-247, train_segmentation.py:368)
-def _supervised_fast_path(model, criterion, optimizer, add_criterion, device, use_depth=False):
-    """The settings of the shipped train_segmentation.py runs that supervised.GraphedSupervisedStep computes: the drop-in two-head
-    ESPDNet-UE, the drop-in SegmentationLoss('ce'), no additional criterion, plain momentum SGD over the script's 2 or 3 learning-rate
-    groups, a CUDA device.  RGB-D batches (use_depth) take the restated body."""
-    from . import losses, models
-    if _FORCE_RESTATED or add_criterion is not None or use_depth:
-        return False
-    if type(model) is not models.ESPDNetwithUncertaintyEstimation or getattr(model, 'aux_layer', -1) < 0:
+def _graphed_sgd_path(model_ok, criterion, optimizer, add_criterion, device, use_depth):
+    """The settings of the shipped train_segmentation.py runs that supervised.GraphedSupervisedStep computes, for a model that passed
+    the caller's test (`model_ok`): the drop-in SegmentationLoss('ce'), no additional criterion, plain momentum SGD over the script's
+    2 or 3 learning-rate groups, a CUDA device.  RGB-D batches (use_depth) take the restated body."""
+    from . import losses
+    if _FORCE_RESTATED or add_criterion is not None or use_depth or not model_ok:
         return False
     if type(criterion) is not losses.SegmentationLoss or criterion.loss_type != 'ce':
         return False
@@ -274,6 +272,13 @@ def _supervised_fast_path(model, criterion, optimizer, add_criterion, device, us
         return torch.device(device).type == 'cuda'
     except (RuntimeError, TypeError):
         return False
+
+
+def _supervised_fast_path(model, criterion, optimizer, add_criterion, device, use_depth=False):
+    """_graphed_sgd_path for train_seg_ue: the drop-in two-head ESPDNet-UE with its auxiliary head."""
+    from . import models
+    two_heads = type(model) is models.ESPDNetwithUncertaintyEstimation and getattr(model, 'aux_layer', -1) >= 0
+    return _graphed_sgd_path(two_heads, criterion, optimizer, add_criterion, device, use_depth)
 
 
 def _train_seg_ue_fast(model, dataset_loader, optimizer, criterion, device, meters, state, heads=2):
@@ -388,24 +393,10 @@ def train_seg_ue(model, dataset_loader, optimizer, criterion, num_classes, epoch
 
 # ------------------------------------------------------------- train_seg() (utilities/train_eval_seg.py:16-91, train_segmentation.py:370-372)
 def _single_head_fast_path(model, criterion, optimizer, add_criterion, device, use_depth=False):
-    """_supervised_fast_path for the single-head loop: the drop-in ESPNetv2Segmentation or ESPDNetSegmentation, the drop-in
-    SegmentationLoss('ce'), no additional criterion, no depth batch, plain momentum SGD over 2 or 3 groups, a CUDA device."""
-    from . import losses, models
-    if _FORCE_RESTATED or add_criterion is not None or use_depth:
-        return False
-    if type(model) not in (models.ESPNetv2Segmentation, models.ESPDNetSegmentation):
-        return False
-    if type(criterion) is not losses.SegmentationLoss or criterion.loss_type != 'ce':
-        return False
-    if type(optimizer) is not torch.optim.SGD or len(optimizer.param_groups) not in (2, 3):
-        return False
-    for g in optimizer.param_groups:
-        if g.get('dampening', 0) != 0 or g.get('nesterov', False) or g.get('maximize', False):
-            return False
-    try:
-        return torch.device(device).type == 'cuda'
-    except (RuntimeError, TypeError):
-        return False
+    """_graphed_sgd_path for train_seg: the drop-in ESPNetv2Segmentation or ESPDNetSegmentation."""
+    from . import models
+    one_head = type(model) in (models.ESPNetv2Segmentation, models.ESPDNetSegmentation)
+    return _graphed_sgd_path(one_head, criterion, optimizer, add_criterion, device, use_depth)
 
 
 def _train_seg_restated(model, dataset_loader, optimizer, criterion, device, use_depth, add_criterion, weight, meters):

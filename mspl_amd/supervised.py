@@ -21,45 +21,43 @@ import os
 import torch
 
 from . import autograd as ag
-from . import dist as mdist
 from . import layers
 from ._native import check, lib
 from .ops import _p, _stream
+from .steps import FlatOptimizer, GraphedStep, run_step
 from .training import TrainMeters
 
 FLOOD_LEVEL = 0.015          # utilities/train_eval_seg.py:178
 
 
-class FlatSGD:
+class FlatSGD(FlatOptimizer):
     """torch.optim.SGD semantics (momentum, L2 weight_decay, dampening 0, no Nesterov; parameters whose gradient is None
-    are skipped) over torch-style parameter groups `[{'params': iterable, 'lr': float}, ...]`.  Build it AFTER the first
-    backward, like FlatAdam.  A parameter listed in two groups raises, as torch.optim does."""
+    are skipped) over torch-style parameter groups `[{'params': iterable, 'lr': float}, ...]`, laid out group after group in the
+    flat buffers (steps.FlatOptimizer: built AFTER the first backward).  A parameter listed in two groups raises, as torch.optim
+    does."""
+
+    STATE = ('buf',)
 
     def __init__(self, params, lr, momentum=0.0, weight_decay=0.0):
         groups = list(params)
         if groups and not isinstance(groups[0], dict):
             groups = [{'params': groups}]
-        self.param_groups, seen, flat = [], set(), []
+        param_groups, seen, flat = [], set(), []
         for g in groups:
             ps = [p for p in g['params'] if p.requires_grad and p.grad is not None]
             for p in ps:
                 if id(p) in seen:
                     raise ValueError('some parameters appear in more than one parameter group')
                 seen.add(id(p))
-            self.param_groups.append({'params': ps, 'lr': g.get('lr', lr), 'momentum': g.get('momentum', momentum),
-                                      'weight_decay': g.get('weight_decay', weight_decay)})
+            param_groups.append({'params': ps, 'lr': g.get('lr', lr), 'momentum': g.get('momentum', momentum),
+                                 'weight_decay': g.get('weight_decay', weight_decay)})
             flat += ps
-        if not flat:
-            raise RuntimeError('FlatSGD: run one backward before constructing the optimizer (no parameter has a gradient)')
-        self.bucket = mdist.GradBucket(flat, with_params=True)            # the flat layout shared with FlatAdam and the all-reduce
-        self.flat_p, self.flat_g = self.bucket.flat_p, self.bucket.flat
-        self.buf = torch.zeros_like(self.flat_p)
+        super().__init__(flat)
+        self.param_groups = param_groups
         first = 0
         for g in self.param_groups:
             g['_lo'], g['_hi'] = self.bucket.span(first, len(g['params']))
             first += len(g['params'])
-        self.params = flat
-        self.step_count = 0
 
     def reset(self, groups=None):
         """Start over as a fresh torch.optim.SGD would (train_segmentation.py builds one per run): zero momentum buffer and the
@@ -73,11 +71,7 @@ class FlatSGD:
                 for k in ('lr', 'momentum', 'weight_decay'):
                     if k in src:
                         g[k] = src[k]
-        self.buf.zero_()
-        self.step_count = 0
-
-    def zero_grad(self):
-        self.flat_g.zero_()
+        super().reset()
 
     def same_partition(self, groups):
         """True when torch-style `groups` split this optimizer's parameters the way it was built: as many groups, and every
@@ -87,22 +81,6 @@ class FlatSGD:
             return False
         return all(set(id(p) for p in mine['params']) <= set(id(p) for p in theirs['params'])
                    for mine, theirs in zip(self.param_groups, groups))
-
-    def reattach(self):
-        """Make every parameter's .grad the view of the flat gradient buffer again (another optimizer's zero_grad() sets it to None
-        and autograd then allocates a tensor of its own, which this optimizer would never read).  Raises when a parameter's storage
-        no longer is its view of the flat parameter buffer (a model moved or re-created since)."""
-        b = self.bucket
-        for p, off in zip(b.params, b.offsets):
-            if p.data_ptr() != b.flat_p.data_ptr() + 4 * off:
-                raise RuntimeError('FlatSGD: a parameter no longer lives in the flat parameter buffer (the model was moved or its '
-                                   'tensors replaced); build a new step')
-            g = p.grad
-            if g is None or g.data_ptr() != b.flat.data_ptr() + 4 * off:
-                p.grad = b.flat[off:off + p.numel()].view_as(p)
-
-    def all_reduce_grads(self):
-        self.bucket.all_reduce()
 
     def step(self):
         first = 1 if self.step_count == 0 else 0
@@ -180,10 +158,15 @@ def _fused_loss(criterion, add_criterion, meters):
     return meters is not None and add_criterion is None and type(criterion) is losses.SegmentationLoss
 
 
-def _sgd_groups(param_groups):
-    """A caller's torch.optim.SGD groups as FlatSGD groups: same parameters, same group order."""
-    return [{'params': list(g['params']), 'lr': g['lr'], 'momentum': g.get('momentum', 0.0),
-             'weight_decay': g.get('weight_decay', 0.0)} for g in param_groups]
+def _flat_sgd(model, param_groups, lr, lr_mult, use_depth, momentum, weight_decay):
+    """The FlatSGD of a first step: over a caller's torch.optim.SGD groups when given (same parameters, same group order), over
+    segmentation_param_groups otherwise."""
+    if param_groups is None:
+        groups = segmentation_param_groups(model, lr, lr_mult, use_depth)
+    else:
+        groups = [{'params': list(g['params']), 'lr': g['lr'], 'momentum': g.get('momentum', 0.0),
+                   'weight_decay': g.get('weight_decay', 0.0)} for g in param_groups]
+    return FlatSGD(groups, lr=lr * lr_mult, momentum=momentum, weight_decay=weight_decay)
 
 
 def train_seg_ue_step(model, inputs, target, criterion, optimizer=None, depth=None, add_criterion=None, weight=1.0,
@@ -193,46 +176,29 @@ def train_seg_ue_step(model, inputs, target, criterion, optimizer=None, depth=No
     optimizer=None on the first call: it is built after the first backward from segmentation_param_groups, or from
     `param_groups` (a caller's torch.optim.SGD groups: same parameters, same order) when given.  meters: a SupervisedMeters the
     iteration is added to -- inside the loss launches for SegmentationLoss('ce') without add_criterion, by meters.add() otherwise."""
-    if optimizer is not None:
-        optimizer.zero_grad()
-    tr = getattr(optimizer, 'transposer', None)
-    with torch.enable_grad(), ag.grad_sinks(), (tr.active() if tr is not None else ag.collect_conv_weights()) as got:
-        layers.prefold_frozen_bn(model)
-        outputs = two_head_outputs(model, inputs, depth)
-        if meters is None:
-            loss = criterion(outputs, target).mean()
-            if add_criterion is not None:
-                loss = loss + add_criterion(inputs, outputs) * weight
-            loss = flood(loss, b)
-        else:
-            loss = _metered_loss(criterion, outputs, target, inputs, add_criterion, weight, b, meters)
-        loss.backward()
-    if meters is not None:
-        meters.count(inputs.shape[0])
-    if optimizer is None:
-        groups = _sgd_groups(param_groups) if param_groups is not None else segmentation_param_groups(model, lr, lr_mult, depth is not None)
-        optimizer = FlatSGD(groups, lr=lr * lr_mult, momentum=momentum, weight_decay=weight_decay)
-        optimizer.transposer = ag.WeightTransposer(got)      # (after FlatSGD: the parameters now live in its flat buffer)
-    optimizer.all_reduce_grads()
-    optimizer.step()
-    return loss.detach(), outputs.detach(), optimizer
+    return run_step(model, optimizer, inputs.shape[0],
+                    lambda: _two_head_loss(model, inputs, target, depth, criterion, add_criterion, weight, b, meters),
+                    lambda: _flat_sgd(model, param_groups, lr, lr_mult, depth is not None, momentum, weight_decay), meters)
 
 
-def _metered_loss(criterion, outputs, target, inputs, add_criterion, weight, b, meters, cw=None):
-    """Loss of the iteration with `meters` filled (the step count stays with the caller).  cw: the class-weight tensor the fused node
-    reads (a graph passes its own static copy)."""
+def _two_head_loss(model, inputs, target, depth, criterion, add_criterion, weight, b, meters, cw=None):
+    """(flooded loss, `main + 0.5 * aux` logits) of one train_seg_ue iteration (utilities/train_eval_seg.py:185-221) with `meters`
+    filled when given (the step count stays with the caller).  cw: the class-weight tensor the fused node reads (a graph passes its
+    own static copy)."""
+    outputs = two_head_outputs(model, inputs, depth)
     if _fused_loss(criterion, add_criterion, meters):
         if cw is None and criterion.class_wts is not None:
             cw = criterion.class_wts.to(outputs.device)
-        return ag.flooded_ce_meters(outputs, target, cw, int(criterion.ignore_idx), b, meters)
+        return ag.flooded_ce_meters(outputs, target, cw, int(criterion.ignore_idx), b, meters), outputs
     loss = criterion(outputs, target).mean()
     loss2 = None
     if add_criterion is not None:
         loss2 = add_criterion(inputs, outputs) * weight
         loss = loss + loss2
     loss = flood(loss, b)
-    meters.add(outputs, target, loss, inputs.shape[0], extra=loss2)
-    return loss
+    if meters is not None:
+        meters.add(outputs, target, loss, inputs.shape[0], extra=loss2)
+    return loss, outputs
 
 
 def _head_loss(model, criterion, add_criterion):
@@ -274,32 +240,20 @@ def train_seg_step(model, inputs, target, criterion, optimizer=None, depth=None,
     ESPDNetSegmentation) in train() mode; there is no flooding.  Returns (loss, the logits the loss was taken on, detached -- the
     low-resolution head with SegmentationLoss('ce') alone, the full-size output otherwise --, optimizer).  optimizer, param_groups
     and meters as in train_seg_ue_step; ce_at_head as in _single_head_loss."""
-    if optimizer is not None:
-        optimizer.zero_grad()
-    tr = getattr(optimizer, 'transposer', None)
-    with torch.enable_grad(), ag.grad_sinks(), (tr.active() if tr is not None else ag.collect_conv_weights()) as got:
-        layers.prefold_frozen_bn(model)
-        loss, outputs = _single_head_loss(model, inputs, target, depth, criterion, add_criterion, weight, meters, ce_at_head=ce_at_head)
-        loss.backward()
-    if meters is not None:
-        meters.count(inputs.shape[0])
-    if optimizer is None:
-        groups = _sgd_groups(param_groups) if param_groups is not None else segmentation_param_groups(model, lr, lr_mult, depth is not None)
-        optimizer = FlatSGD(groups, lr=lr * lr_mult, momentum=momentum, weight_decay=weight_decay)
-        optimizer.transposer = ag.WeightTransposer(got)      # (after FlatSGD: the parameters now live in its flat buffer)
-    optimizer.all_reduce_grads()
-    optimizer.step()
-    return loss.detach(), outputs.detach(), optimizer
+    return run_step(model, optimizer, inputs.shape[0],
+                    lambda: _single_head_loss(model, inputs, target, depth, criterion, add_criterion, weight, meters, ce_at_head=ce_at_head),
+                    lambda: _flat_sgd(model, param_groups, lr, lr_mult, depth is not None, momentum, weight_decay), meters)
 
 
-class GraphedSupervisedStep:
-    """train_seg_ue_step with zero_grad + forward + loss + backward replayed as ONE hipGraph (the iteration is ~900 launches);
-    the gradient all-reduce and the SGD kernels (their learning rates change per epoch) stay outside.  The first call runs one
-    eager iteration (reveals the gradient-bearing parameters, builds FlatSGD, consumes SGD's first-step rule) and captures;
-    shapes are fixed at construction.  BatchNorm running statistics and num_batches_tracked advance inside the graph.
+class GraphedSupervisedStep(GraphedStep):
+    """train_seg_ue_step on steps.GraphedStep (the iteration is ~900 launches; the SGD kernels stay outside the graph, their
+    learning rates change per epoch).  The eager iteration of the constructor consumes SGD's first-step rule.  BatchNorm running
+    statistics and num_batches_tracked advance inside the graph.
 
     heads=1: the same skeleton around train_seg_step (a single-head model, no flooding: `b` is unused; the loss through
     _single_head_loss with `ce_at_head`)."""
+
+    SNAPSHOT_BUFFERS = True          # train()-mode BatchNorm: the running statistics belong to the entry state
 
     def __init__(self, model, inputs, target, criterion, depth=None, lr=0.009, lr_mult=10.0, momentum=0.9, weight_decay=4e-5,
                  b=FLOOD_LEVEL, *, meters=None, consume_first_batch=True, param_groups=None, heads=2, ce_at_head=None):
@@ -314,49 +268,22 @@ class GraphedSupervisedStep:
         self.model, self.criterion, self.b = model, criterion, b
         self.meters = meters
         self.heads, self.ce_at_head = heads, ce_at_head
-        entry = None
-        if not consume_first_batch:
-            entry = ([p.detach().clone() for p in model.parameters()], dict((n, t.detach().clone()) for n, t in model.named_buffers()))
-        self.inputs = inputs.detach().clone()
-        self.target = target.detach().clone()
-        self.depth = None if depth is None else depth.detach().clone()
-        if heads == 2:
-            _, _, self.optimizer = train_seg_ue_step(model, self.inputs, self.target, criterion, None, self.depth, None, 1.0, lr, lr_mult,
-                                                     momentum, weight_decay, b, meters=meters, param_groups=param_groups)
-        else:
-            _, _, self.optimizer = train_seg_step(model, self.inputs, self.target, criterion, None, self.depth, None, 1.0, lr, lr_mult,
-                                                  momentum, weight_decay, meters=meters, param_groups=param_groups, ce_at_head=ce_at_head)
         # the class weights the captured loss node reads: a copy of this object's own, refreshed by set_criterion
         self.cw = None
         if self._node_loss(criterion) and criterion.class_wts is not None:
-            self.cw = criterion.class_wts.detach().to(self.inputs.device, torch.float32).clone()
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with layers.graph_capture(self.graph):
-            self.optimizer.zero_grad()
-            with torch.enable_grad(), ag.grad_sinks(), self.optimizer.transposer.active():
-                layers.prefold_frozen_bn(model)
-                if heads == 1:
-                    self.loss, self.outputs = _single_head_loss(model, self.inputs, self.target, self.depth, criterion, None, 1.0, meters,
-                                                                cw=self.cw, ce_at_head=ce_at_head)
-                else:
-                    self.outputs = two_head_outputs(model, self.inputs, self.depth)
-                    if meters is None:
-                        self.loss = flood(criterion(self.outputs, self.target).mean(), b)
-                    else:
-                        self.loss = _metered_loss(criterion, self.outputs, self.target, self.inputs, None, 1.0, b, meters, cw=self.cw)
-                self.loss.backward()
-        self._finish()                                  # the capture did not execute: run the iteration it recorded
-        if entry is not None:
-            with torch.no_grad():
-                for p, p0 in zip(model.parameters(), entry[0]):       # (.data are views of the flat buffer by now: written in place)
-                    p.copy_(p0)
-                for n, t in model.named_buffers():
-                    t.copy_(entry[1][n])
-            self.optimizer.reset()
-            layers.bump_param_epoch()
-        if meters is not None:
-            meters.reset()
+            self.cw = criterion.class_wts.detach().to(inputs.device, torch.float32).clone()
+
+        # (the eager iteration reads the caller's criterion, class weights included, and fills the meters)
+        eager_step, kw = (train_seg_ue_step, {'b': b}) if heads == 2 else (train_seg_step, {'ce_at_head': ce_at_head})
+        self._build([('inputs', inputs), ('target', target), ('depth', depth)],
+                    lambda: eager_step(model, self.inputs, self.target, criterion, None, self.depth, None, 1.0, lr, lr_mult, momentum,
+                                       weight_decay, meters=meters, param_groups=param_groups, **kw)[2], consume_first_batch)
+
+    def _loss(self):
+        if self.heads == 1:
+            return _single_head_loss(self.model, self.inputs, self.target, self.depth, self.criterion, None, 1.0, self.meters,
+                                     cw=self.cw, ce_at_head=self.ce_at_head)
+        return _two_head_loss(self.model, self.inputs, self.target, self.depth, self.criterion, None, 1.0, self.b, self.meters, cw=self.cw)
 
     def _node_loss(self, criterion):
         """True when the captured loss is a node that reads this object's own class-weight tensor."""
@@ -377,17 +304,5 @@ class GraphedSupervisedStep:
             self.cw.copy_(criterion.class_wts.to(self.cw.device, torch.float32))
         self.criterion = criterion
 
-    def _finish(self):
-        self.graph.replay()
-        self.optimizer.all_reduce_grads()
-        self.optimizer.step()
-        if self.meters is not None:
-            self.meters.count(self.inputs.shape[0])
-        return self.loss.detach(), self.outputs.detach()
-
     def __call__(self, inputs, target, depth=None):
-        self.inputs.copy_(inputs)
-        self.target.copy_(target)
-        if self.depth is not None:
-            self.depth.copy_(depth)
-        return self._finish()
+        return super().__call__(inputs, target, depth)

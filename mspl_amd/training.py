@@ -10,16 +10,16 @@ gradient and the two Adam moments in four flat fp32 buffers, so the optimizer is
 gradient exchange ONE all-reduce (mspl_amd.dist).  Parameters whose gradient stays None (depth encoder, fusion gates,
 module_act of strided EESPs: 230 of 570 tensors) are left out, exactly like torch.optim.Adam skips them.
 """
-import ctypes
 import os
 
 import torch
 
 from . import autograd as ag
-from . import dist as mdist
 from . import layers
 from ._native import check, lib
 from .ops import _p, _stream
+from .steps import FlatOptimizer, GraphedStep, run_step
+from .streams import _concurrent_streams
 
 
 def _device_class_weights(class_weights, device, ignore_idx):
@@ -94,7 +94,10 @@ def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=F
     lowres = getattr(model, 'forward_lowres', None) if _LOSS_AT_HEADS else None
     if lowres is not None:
         main, aux = lowres(images)
-        if aux is not None and ag.uw_loss_heads_supported(main.shape[1]):
+        if aux is None:
+            raise RuntimeError('mspl_amd.training.forward_loss: %s returns one head; the uest loss needs the auxiliary head of a '
+                               'two-head model' % type(model).__name__)
+        if ag.uw_loss_heads_supported(main.shape[1]):
             return ag.uw_loss_heads(main, aux, labels, cw, ce_scale, out_scale, root, meters)
         size = tuple(images.shape[2:])
         pred, aux = ag.bilinear(main, size), ag.bilinear(aux, size)
@@ -106,25 +109,17 @@ def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=F
     return loss
 
 
-class FlatAdam:
-    """torch.optim.Adam semantics (lr, betas, eps, L2 weight_decay, bias correction) on flat buffers.
+class FlatAdam(FlatOptimizer):
+    """torch.optim.Adam semantics (lr, betas, eps, L2 weight_decay, bias correction) on flat buffers (steps.FlatOptimizer: built
+    AFTER the first backward)."""
 
-    Build it AFTER the first backward: the parameters that received a gradient define the flat layout.  Parameter
-    .data and .grad are re-pointed to views of the flat buffers (values preserved)."""
+    STATE = ('m', 'v')
 
     def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        try:
-            self.bucket = mdist.GradBucket(params, with_params=True)      # the flat layout shared with FlatSGD and the all-reduce
-        except RuntimeError:
-            raise RuntimeError('FlatAdam: run one backward before constructing the optimizer (no parameter has a gradient)')
-        self.params = self.bucket.params
-        self.flat_p, self.flat_g = self.bucket.flat_p, self.bucket.flat
-        self.m = torch.zeros_like(self.flat_p)
-        self.v = torch.zeros_like(self.flat_p)
+        super().__init__(params)
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         # torch.optim spelling: the reference's adjust_learning_rate writes optimizer.param_groups[0]['lr'] (:1325-1328)
         self.param_groups = [{'lr': lr, 'params': self.params}]
-        self.step_count = 0
 
     @property
     def lr(self):
@@ -134,12 +129,13 @@ class FlatAdam:
     def lr(self, value):
         self.param_groups[0]['lr'] = value
 
-    def zero_grad(self):
-        self.flat_g.zero_()
-
-    def all_reduce_grads(self):
-        """Average gradients over the ranks: one collective on the flat bucket (RCCL over xGMI on GPUs)."""
-        self.bucket.all_reduce()
+    def reset(self, lr=None, betas=None, eps=None, weight_decay=None):
+        """Start over as a fresh torch.optim.Adam would: zero moments and step count; hyper-parameters given are taken over."""
+        super().reset()
+        given = {'lr': lr, 'betas': None if betas is None else tuple(betas), 'eps': eps, 'weight_decay': weight_decay}
+        for name, value in given.items():
+            if value is not None:
+                setattr(self, name, value)
 
     def step(self):
         self.step_count += 1
@@ -165,23 +161,13 @@ def train_step(model, images, labels, class_weights, optimizer=None, ignore_idx=
                ce_scale=20.0, meters=None):
     """One optimisation step; returns (loss tensor, optimizer).  Pass optimizer=None on the first call: it is built
     after the first backward (which reveals the gradient-bearing parameters).  meters: a TrainMeters the step is added to."""
-    if optimizer is not None:
-        optimizer.zero_grad()
-    tr = getattr(optimizer, 'transposer', None)
-    with torch.enable_grad(), ag.grad_sinks(), (tr.active() if tr is not None else ag.collect_conv_weights()) as got:
-        layers.prefold_frozen_bn(model)
-        loss = forward_loss(model, images, labels, _device_class_weights(class_weights, images.device, ignore_idx), ce_scale,
-                            meters=meters)
-        loss.backward()
-    if meters is not None:
-        meters.count(images.shape[0])
-    if optimizer is None:
-        optimizer = FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay)
-        # (built after FlatAdam: the parameters now live in its flat buffer)
-        optimizer.transposer = ag.WeightTransposer(got)
-    optimizer.all_reduce_grads()
-    optimizer.step()
-    return loss.detach(), optimizer
+    def loss_fn():
+        return forward_loss(model, images, labels, _device_class_weights(class_weights, images.device, ignore_idx), ce_scale,
+                            meters=meters), None
+
+    loss, _, optimizer = run_step(model, optimizer, images.shape[0], loss_fn,
+                                  lambda: FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay), meters)
+    return loss, optimizer
 
 
 SETTLE_THRESHOLD = 0.55      # four lanes overlapping take 0.44-0.45 of the same graphs back to back; two lanes sharing a queue ~0.7
@@ -203,20 +189,16 @@ def settle_seating(serial_ms, first_ms, measure, new_candidate, attempts=3, thre
     return {'seating': best, 'lanes_ms': best_ms, 'settled': bool(best_ms <= threshold * serial_ms), 'attempts': used}
 
 
-class GraphedTrainStep:
-    """train_step with zero_grad + forward + loss + backward replayed as hipGraphs (the step is ~1400 launches of 5-100 us; eager
-    issue from Python is slower than the GPU executes them).  The gradient all-reduce and the Adam kernel stay outside the graphs,
-    so the same object serves N = 1 and N > 1.
+class GraphedTrainStep(GraphedStep):
+    """train_step on steps.GraphedStep (the step is ~1400 launches of 5-100 us; eager issue from Python is slower than the GPU
+    executes them).
 
     lanes = 1: ONE graph.  lanes = L > 1: the batch is cut into L micro-batches that run as L graphs on L streams AT THE SAME TIME
     (the kernels of a batch-16 step are too small to fill the chip; graphs on separate streams overlap, branches inside one
     graph did not).  Same step: BatchNorm is frozen, the loss is a plain mean over the pixels of the batch (K11: 1 / (N*H*W)), so
     each lane back-propagates loss_lane / L and every parameter-gradient kernel adds into the shared flat gradient buffer with
     atomics (autograd.grad_sinks); only the floating-point summation order differs.  A parameter whose gradient would go through
-    autograd's (non-atomic) AccumulateGrad in a lane is refused at construction.
-
-    The first call runs one eager step (it reveals the gradient-bearing parameters and builds FlatAdam) and captures;
-    later calls copy the batch into static buffers and replay.  Shapes are fixed at construction."""
+    autograd's (non-atomic) AccumulateGrad in a lane is refused at construction."""
 
     def __init__(self, model, images, labels, class_weights, ignore_idx=None, lr=5e-4, weight_decay=5e-4, ce_scale=20.0, lanes=1,
                  meters=None, consume_first_batch=True):
@@ -225,99 +207,70 @@ class GraphedTrainStep:
         back to their values on entry, both Adam moments, the step count and the meters are zeroed, so the first call is step 1 (a
         training loop applies each batch exactly once; the default applies the construction batch twice: an eager step, then the
         captured one)."""
-        self.model = model
-        self.meters = meters
-        entry = None if consume_first_batch else [p.detach().clone() for p in model.parameters()]
-        self.images = images.detach().clone()
-        self.labels = labels.detach().to(torch.int64).clone()
+        self.model, self.meters = model, meters
         self.cw = _device_class_weights(class_weights, images.device, ignore_idx)
         self.ce_scale = ce_scale
-        B = self.images.shape[0]
-        self.lanes = lanes if (lanes > 1 and B % lanes == 0) else 1
-        _, self.optimizer = train_step(model, self.images, self.labels, class_weights, None, ignore_idx, lr, weight_decay,
-                                       ce_scale)
-        torch.cuda.synchronize()
-        tr = self.optimizer.transposer
+        self.lanes = lanes if (lanes > 1 and images.shape[0] % lanes == 0) else 1
+        # (the eager step gets the caller's class weights and no meters; the capture reads this object's own `cw`)
+        self._build([('images', images), ('labels', labels.to(torch.int64))],
+                    lambda: train_step(model, self.images, self.labels, class_weights, None, ignore_idx, lr, weight_decay, ce_scale)[1],
+                    consume_first_batch)
+
+    def _lane_loss(self, images, labels, out_scale=1.0):
+        return forward_loss(self.model, images, labels, self.cw, self.ce_scale, out_scale=out_scale, root=True, meters=self.meters)
+
+    def _loss(self):
+        return self._lane_loss(self.images, self.labels), None
+
+    def _capture(self):
         if self.lanes == 1:
-            self.graph = torch.cuda.CUDAGraph()
-            with layers.graph_capture(self.graph):
-                self.optimizer.zero_grad()
-                with torch.enable_grad(), ag.grad_sinks(), tr.active():
-                    layers.prefold_frozen_bn(model)
-                    self.loss = forward_loss(model, self.images, self.labels, self.cw, ce_scale, root=True, meters=meters)
-                    self.loss.backward()
-        else:
-            # what every lane needs first: zeroed gradients, this step's transposed weights and folded BatchNorms (their tensors live
-            # in this graph's pool, the lanes' graphs read them)
-            self.graph = torch.cuda.CUDAGraph()
-            with layers.graph_capture(self.graph):
-                self.optimizer.zero_grad()
-                tr.run()
-                with torch.no_grad():
-                    layers.prefold_frozen_bn(model)
-            b = B // self.lanes
-            # streams that really run side by side (HIP multiplexes streams onto a few hardware queues; two lanes on one queue run one
-            # after the other, and four serialised micro-batches are SLOWER than the one-graph step: 12.2 vs 9.0 ms, both seen in one
-            # process with plain new streams, depending on how many streams existed before)
-            from .uest import _concurrent_streams
-            self.streams = _concurrent_streams(self.lanes, self.images.device)
-            self.lane_graphs, self.lane_losses = [], []
-            stray = []
-            # (a tensor hook sees None when the op accumulated into the sink itself, a tensor when autograd is about to add one)
-            hooks = [p.register_hook(lambda g_: stray.append(1) if g_ is not None else None) for p in self.optimizer.params]
-            try:
-                for i, st in enumerate(self.streams):
-                    st.wait_stream(torch.cuda.current_stream())
-                    g = torch.cuda.CUDAGraph()
-                    with layers.graph_capture(g, stream=st):
-                        with torch.enable_grad(), ag.grad_sinks(), tr.active(refresh=False):
-                            loss = forward_loss(model, self.images[i * b:(i + 1) * b], self.labels[i * b:(i + 1) * b], self.cw, ce_scale,
-                                                out_scale=1.0 / self.lanes, root=True, meters=meters)
-                            loss.backward()
-                    self.lane_graphs.append(g)
-                    self.lane_losses.append(loss)
-            finally:
-                for h in hooks:
-                    h.remove()
-            if stray:
-                raise RuntimeError('GraphedTrainStep(lanes=%d): %d parameter gradients went through AccumulateGrad instead of an '
-                                   'atomic gradient sink; concurrent lanes would race on them' % (self.lanes, len(stray)))
-        if self.lanes > 1:
-            # the capture did not execute: the lanes read this step's transposed weights and BatchNorm folds from self.graph's pool,
-            # so it runs once before the lanes are timed (they would otherwise run on uninitialised memory)
-            self.graph.replay()
-            self._settle_streams()
-        self._finish()      # run the step the capture recorded
-        if entry is not None:
+            return super()._capture()
+        tr = self.optimizer.transposer
+        # what every lane needs first: zeroed gradients, this step's transposed weights and folded BatchNorms (their tensors live
+        # in this graph's pool, the lanes' graphs read them)
+        self.graph = torch.cuda.CUDAGraph()
+        with layers.graph_capture(self.graph):
+            self.optimizer.zero_grad()
+            tr.run()
             with torch.no_grad():
-                for p, p0 in zip(model.parameters(), entry):      # (.data are views of the flat buffer by now: written in place)
-                    p.copy_(p0)
-            self.optimizer.m.zero_()
-            self.optimizer.v.zero_()
-            self.optimizer.step_count = 0
-            layers.bump_param_epoch()
-        if meters is not None:
-            meters.reset()
+                layers.prefold_frozen_bn(self.model)
+        b = self.images.shape[0] // self.lanes
+        # streams that really run side by side (HIP multiplexes streams onto a few hardware queues; two lanes on one queue run one
+        # after the other, and four serialised micro-batches are SLOWER than the one-graph step: 12.2 vs 9.0 ms, both seen in one
+        # process with plain new streams, depending on how many streams existed before)
+        self.streams = _concurrent_streams(self.lanes, self.images.device)
+        self.lane_graphs, self.lane_losses = [], []
+        stray = []
+        # (a tensor hook sees None when the op accumulated into the sink itself, a tensor when autograd is about to add one)
+        hooks = [p.register_hook(lambda g_: stray.append(1) if g_ is not None else None) for p in self.optimizer.params]
+        try:
+            for i, st in enumerate(self.streams):
+                st.wait_stream(torch.cuda.current_stream())
+                g = torch.cuda.CUDAGraph()
+                with layers.graph_capture(g, stream=st):
+                    with torch.enable_grad(), ag.grad_sinks(), tr.active(refresh=False):
+                        loss = self._lane_loss(self.images[i * b:(i + 1) * b], self.labels[i * b:(i + 1) * b], 1.0 / self.lanes)
+                        loss.backward()
+                self.lane_graphs.append(g)
+                self.lane_losses.append(loss)
+        finally:
+            for h in hooks:
+                h.remove()
+        if stray:
+            raise RuntimeError('GraphedTrainStep(lanes=%d): %d parameter gradients went through AccumulateGrad instead of an '
+                               'atomic gradient sink; concurrent lanes would race on them' % (self.lanes, len(stray)))
+        # the capture did not execute: the lanes read this step's transposed weights and BatchNorm folds from self.graph's pool,
+        # so it runs once before the lanes are timed (they would otherwise run on uninitialised memory)
+        self.graph.replay()
+        self._settle_streams()
 
     def set_class_weights(self, class_weights, ignore_idx=None):
         """New class weights (a relabelling round, uest_seg_multi_os.py:527-530): copied into the tensor the graphs read."""
         self.cw.copy_(_device_class_weights(class_weights, self.cw.device, ignore_idx))
 
     def reset_optimizer(self, lr=None, betas=None, eps=None, weight_decay=None):
-        """Start over as a fresh torch.optim.Adam would: zero moments and step count (the script builds a new optimizer per round,
-        :594-598); hyper-parameters given are taken over."""
-        opt = self.optimizer
-        opt.m.zero_()
-        opt.v.zero_()
-        opt.step_count = 0
-        if lr is not None:
-            opt.lr = lr
-        if betas is not None:
-            opt.betas = tuple(betas)
-        if eps is not None:
-            opt.eps = eps
-        if weight_decay is not None:
-            opt.weight_decay = weight_decay
+        """FlatAdam.reset (the script builds a new optimizer per round, :594-598)."""
+        self.optimizer.reset(lr, betas, eps, weight_decay)
 
     def _lanes_ms(self, streams, reps=2):
         """Wall time of one replay of every lane graph, lane i on streams[i % len(streams)] (the gradients they add up are thrown away by
@@ -346,7 +299,6 @@ class GraphedTrainStep:
         clearly less than the same graphs back to back on one stream; the best seating seen is kept (`settle_seating` is the decision,
         a pure function of the timings: tests/test_host.py drives it with injected ones).  The lanes are timed on REAL data: the
         caller has replayed `self.graph` (zeroed gradients, this step's transposed weights and BatchNorm folds) before."""
-        from .uest import _concurrent_streams
         self._lanes_ms(self.streams, 1)                                  # warm-up
         serial = self._lanes_ms(self.streams[:1])
         pool = [self.streams]           # candidate stream sets: bounded, and the losers are dropped with this list
@@ -366,7 +318,7 @@ class GraphedTrainStep:
             warnings.warn('GraphedTrainStep(lanes=%d): the lane graphs did not overlap after %d re-seatings (%.2f ms against %.2f ms '
                           'back to back); the step runs on the best seating seen' % (self.lanes, d['attempts'], d['lanes_ms'], serial))
 
-    def _finish(self):
+    def _replay(self):
         self.graph.replay()
         if self.lanes > 1:
             cur = torch.cuda.current_stream()
@@ -378,13 +330,3 @@ class GraphedTrainStep:
             for st in self.streams:
                 cur.wait_stream(st)
             self.loss = torch.stack([l.detach() for l in self.lane_losses]).sum()
-        self.optimizer.all_reduce_grads()
-        self.optimizer.step()
-        if self.meters is not None:
-            self.meters.count(self.images.shape[0])
-        return self.loss.detach()
-
-    def __call__(self, images, labels):
-        self.images.copy_(images)
-        self.labels.copy_(labels)
-        return self._finish()
