@@ -287,6 +287,45 @@ int mspl_pyrpool_fused_fwd(const float* x, int32_t N, int32_t P, int32_t h, int3
                            const float* const* down_e, const float* br_scale, const float* br_shift,
                            const float* br_alpha, const float* merge_w, const mspl_epilogue_t* ep,
                            float* out, void* stream);
+/* The register-streaming form of K6 (branches up, up, same, down, down; w >= 40; N * P a multiple of 4; stencils of 3 or 5 taps)
+ * uses two sets of stencil coefficients that depend on (h, w, hs[0..1], ws[0..1]) alone: the row tables A and the column tables G.
+ * mspl_pyrpool_fused_fwd computes them in every workgroup of every launch; the three entry points below compute them once.
+ *   mspl_pyr_stream_tables_bytes: bytes of the table block of a geometry, 0 when the streaming form does not cover it.
+ *   mspl_pyr_stream_tables_build: one small launch that fills `tables` (device memory, 16-byte aligned, `bytes` as returned above)
+ *     with the bits the kernel computes itself otherwise; the library notes which geometry the block at this address holds.
+ *   mspl_pyrpool_fused_tab_fwd: mspl_pyrpool_fused_fwd reading that block; bit-identical output.  Its epilogue is what the
+ *     streaming form applies, as plain arguments: ep_scale / ep_shift / ep_alpha (out_ctot entries each, any may be NULL), the
+ *     destination's out_ctot channels and first channel out_coff, launch_flags = MSPL_LAUNCH_*; callers with further epilogue
+ *     terms use mspl_pyrpool_fused_fwd.  tables == NULL: exactly mspl_pyrpool_fused_fwd with that epilogue.  A block built for another geometry, or an address nothing was built at, is MSPL_ERR_BAD_SHAPE and
+ *     nothing is launched.  Where the streaming form leaves the launch to the other forms, the block is not looked at.
+ *     With the block a wave's row segment may be up to 72 rows long (19 without): see mspl_pyrpool_stream_plan. */
+int64_t mspl_pyr_stream_tables_bytes(int32_t h, int32_t w, int32_t nb, const int32_t* hs, const int32_t* ws);
+int mspl_pyr_stream_tables_build(int32_t h, int32_t w, int32_t nb, const int32_t* hs, const int32_t* ws, float* tables,
+                                 int64_t bytes, void* stream);
+int mspl_pyrpool_fused_tab_fwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb,
+                               const int32_t* hs, const int32_t* ws, const float* const* stage_w,
+                               const float* const* down_e, const float* br_scale, const float* br_shift,
+                               const float* br_alpha, const float* merge_w, const float* ep_scale, const float* ep_shift,
+                               const float* ep_alpha, int32_t out_ctot, int32_t out_coff, uint32_t launch_flags, float* out,
+                               const float* tables, void* stream);
+/* What the streaming form decides for these shapes, from the host function its launcher calls itself (no device call).  out:
+ * MSPL_PYR_STREAM_PLAN_LEN entries, all 0 when the shapes are left to the other forms.  Pointers are not seen here: the launcher
+ * also declines x / out that are not 8-byte aligned at PXL = 2, missing weights or maps and epilogues beyond scale/shift/PReLU. */
+#define MSPL_PYR_STREAM_PLAN_TAKEN 0            /* 1: the streaming form takes the shapes */
+#define MSPL_PYR_STREAM_PLAN_T0 1               /* taps of the two up branches' stencils: 3 or 5 */
+#define MSPL_PYR_STREAM_PLAN_T1 2
+#define MSPL_PYR_STREAM_PLAN_PXL 3              /* adjacent columns per lane: 1 (w <= 62) or 2 */
+#define MSPL_PYR_STREAM_PLAN_NCB 4              /* column blocks */
+#define MSPL_PYR_STREAM_PLAN_CBW 5              /* output columns per block: 62 * PXL */
+#define MSPL_PYR_STREAM_PLAN_SEG 6              /* with tables: output rows per segment */
+#define MSPL_PYR_STREAM_PLAN_NSEG 7             /*   segments per plane */
+#define MSPL_PYR_STREAM_PLAN_WAVES 8            /*   waves of the launch */
+#define MSPL_PYR_STREAM_PLAN_SEG_INKERNEL 9     /* without tables (mspl_pyrpool_fused_fwd, the training forward): the same three */
+#define MSPL_PYR_STREAM_PLAN_NSEG_INKERNEL 10
+#define MSPL_PYR_STREAM_PLAN_WAVES_INKERNEL 11
+#define MSPL_PYR_STREAM_PLAN_LEN 12
+int mspl_pyrpool_stream_plan(int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs, const int32_t* ws,
+                             int32_t* out);
 
 /* ---- fused EfficientPyrPool body on the training path (nn_layers/efficient_pyramid_pool.py:39-58 + its autograd backward) ----
  * Forward: mspl_pyrpool_fused_fwd that also keeps what the backward needs: zcat (N, nb*P, h, w) = the branch values BEFORE

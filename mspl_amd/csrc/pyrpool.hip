@@ -374,7 +374,11 @@ int pyrpool_sep_try(const float* x, int N, int P, int h, int w, int nb, const in
 int pyrpool_stream_try(const float* x, int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws,
                        const float* const* stage_w, const float* const* down_e, const float* br_scale,
                        const float* br_shift, const float* br_alpha, const float* merge_w, const Epi& e, float* out,
-                       hipStream_t stream, float* zcat = nullptr);    // pyrpool_stream.hip
+                       hipStream_t stream, float* zcat = nullptr, const float* tab = nullptr);    // pyrpool_stream.hip
+int pyrpool_stream_tables_build(int h, int w, int nb, const int32_t* hs, const int32_t* ws, float* tab, int64_t bytes,
+                                hipStream_t stream);
+int64_t pyrpool_stream_tables_bytes(int h, int w, int nb, const int32_t* hs, const int32_t* ws);
+void pyrpool_stream_plan(int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws, int32_t* out);
 
 }  // namespace mspl
 
@@ -384,7 +388,7 @@ static int pyrpool_fused_launch(const float* x, int32_t N, int32_t P, int32_t h,
                                const int32_t* hs, const int32_t* ws, const float* const* stage_w,
                                const float* const* down_e, const float* br_scale, const float* br_shift,
                                const float* br_alpha, const float* merge_w, const mspl_epilogue_t* ep,
-                               float* out, float* zcat, void* stream, bool dry = false) {
+                               float* out, float* zcat, void* stream, bool dry = false, const float* tab = nullptr) {
     // dry: shape / LDS planning only (mspl_pyrpool_fused_train_fits): no pointer is looked at, nothing is launched
     MSPL_REQUIRE(dry || (x && hs && ws && stage_w && down_e && br_scale && br_shift && br_alpha && merge_w && out),
                  MSPL_ERR_NULL_POINTER, "pyrpool_fused: null pointer");
@@ -397,7 +401,7 @@ static int pyrpool_fused_launch(const float* x, int32_t N, int32_t P, int32_t h,
         if (!force_tables) {
             // (the training forward -- zcat wanted -- exists in the streaming and in the table form)
             const int rc3 = pyrpool_stream_try(x, N, P, h, w, nb, hs, ws, stage_w, down_e, br_scale, br_shift, br_alpha, merge_w,
-                                               make_epi(ep, P, h * w), out, (hipStream_t)stream, zcat);
+                                               make_epi(ep, P, h * w), out, (hipStream_t)stream, zcat, tab);
             if (rc3 <= 0) return rc3;
             if (!zcat) {
                 const int rc = pyrpool_sep_try(x, N, P, h, w, nb, hs, ws, stage_w, down_e, br_scale, br_shift, br_alpha, merge_w,
@@ -484,6 +488,41 @@ extern "C" int mspl_pyrpool_fused_fwd(const float* x, int32_t N, int32_t P, int3
                                       float* out, void* stream) {
     return pyrpool_fused_launch(x, N, P, h, w, nb, hs, ws, stage_w, down_e, br_scale, br_shift, br_alpha, merge_w, ep, out, nullptr,
                                 stream);
+}
+
+extern "C" int mspl_pyrpool_fused_tab_fwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb,
+                                          const int32_t* hs, const int32_t* ws, const float* const* stage_w,
+                                          const float* const* down_e, const float* br_scale, const float* br_shift,
+                                          const float* br_alpha, const float* merge_w, const float* ep_scale,
+                                          const float* ep_shift, const float* ep_alpha, int32_t out_ctot, int32_t out_coff,
+                                          uint32_t launch_flags, float* out, const float* tables, void* stream) {
+    mspl_epilogue_t ep;
+    memset(&ep, 0, sizeof(ep));
+    ep.scale = ep_scale; ep.shift = ep_shift; ep.alpha = ep_alpha;
+    ep.out_ctot = out_ctot; ep.out_coff = out_coff;
+    ep.struct_size = (uint32_t)sizeof(ep); ep.flags = launch_flags;
+    return pyrpool_fused_launch(x, N, P, h, w, nb, hs, ws, stage_w, down_e, br_scale, br_shift, br_alpha, merge_w, &ep, out, nullptr,
+                                stream, false, tables);
+}
+
+extern "C" int64_t mspl_pyr_stream_tables_bytes(int32_t h, int32_t w, int32_t nb, const int32_t* hs, const int32_t* ws) {
+    if (!hs || !ws || h <= 0 || w <= 0) return 0;
+    return pyrpool_stream_tables_bytes(h, w, nb, hs, ws);
+}
+
+extern "C" int mspl_pyr_stream_tables_build(int32_t h, int32_t w, int32_t nb, const int32_t* hs, const int32_t* ws, float* tables,
+                                            int64_t bytes, void* stream) {
+    MSPL_REQUIRE(hs && ws && tables, MSPL_ERR_NULL_POINTER, "pyr_stream_tables: null pointer");
+    MSPL_REQUIRE(h > 0 && w > 0, MSPL_ERR_BAD_SHAPE, "pyr_stream_tables: bad shape %dx%d", h, w);
+    return pyrpool_stream_tables_build(h, w, nb, hs, ws, tables, bytes, (hipStream_t)stream);
+}
+
+extern "C" int mspl_pyrpool_stream_plan(int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs, const int32_t* ws,
+                                        int32_t* out) {
+    MSPL_REQUIRE(hs && ws && out, MSPL_ERR_NULL_POINTER, "pyrpool_stream_plan: null pointer");
+    MSPL_REQUIRE(N > 0 && P > 0 && h > 0 && w > 0, MSPL_ERR_BAD_SHAPE, "pyrpool_stream_plan: bad shape N=%d P=%d %dx%d", N, P, h, w);
+    pyrpool_stream_plan(N, P, h, w, nb, hs, ws, out);
+    return MSPL_OK;
 }
 
 extern "C" int mspl_pyrpool_fused_train_fwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb,

@@ -223,7 +223,10 @@ _FUSED_DOWN_HEAD = os.environ.get('MSPL_DOWN_HEAD', '1') != '0'   # inference: a
 # label pass: the final 1x1 classifier of a decoder head (EfficientPyrPool, last_layer_br=False) is computed by the label epilogue
 # from the head's planes (ops.label_epilogue_planes) instead of a launch of its own
 _FUSED_HEAD_CLASSIFIER = os.environ.get('MSPL_HEAD_CLASSIFIER', '1') != '0'
-_FUSED_DEC_MERGE = True          # inference: skip 3x3 + up-merge + the next pyramid block's projection as one launch (ops.decoder_merge)
+# inference: the pyramid kernel's streaming form reads its stencil tables from memory (built once per map geometry) instead of
+# computing them in every workgroup, and walks longer row segments (ops.pyr_stream_tables); same output bits
+_PYR_STREAM_TABLES = os.environ.get('MSPL_PYR_STREAM_TABLES', '1') != '0'
+_FUSED_DEC_MERGE = True         # inference: skip 3x3 + up-merge + the next pyramid block's projection as one launch (ops.decoder_merge)
 _FUSED_NEXT_PROJ = os.environ.get('MSPL_EESP_NEXT', '1') != '0'   # ... and the following block's proj_1x1 inside that launch
 _FUSED_EESP_TRAIN = os.environ.get('MSPL_FUSED_EESP_TRAIN', '1') != '0'  # EESP block as one autograd node (frozen BatchNorm)
 _FUSED_PYR_TRAIN = os.environ.get('MSPL_FUSED_PYR_TRAIN', '1') != '0'    # pyramid body as one autograd node (frozen BatchNorm)
@@ -765,7 +768,23 @@ class EfficientPyrPool(nn.Module):
         bscale, bshift = bn_fold(br[0])
         mcbr = self.merge_layer[2]
         return ops.pyrpool_fused(x, sizes, stage_ws, down_es, bscale, bshift, br[1].weight, mcbr.cbr[0].weight,
-                                 mcbr.epi())
+                                 mcbr.epi(), tables=self._stream_tables(x, sizes) if _PYR_STREAM_TABLES else None)
+
+    def _stream_tables(self, x, sizes):
+        """Stencil tables of the fused kernel's streaming form for this map geometry: built by the first eager call, kept with the
+        module (no parameter enters them).  None where that form does not take the shapes, and inside a capture that no eager call
+        preceded: the kernel then computes them itself, with the same bits."""
+        N, P, height, width = x.shape
+        key = (x.device, N * P % 4, height, width) + tuple((int(a), int(b)) for a, b in sizes)
+        store = self.__dict__.setdefault('_mspl_pyr_tables', {})
+        if key not in store:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            taken = ops.pyrpool_stream_plan(x.shape, sizes)['taken']
+            store[key] = ops.pyr_stream_tables(height, width, sizes, x.device) if taken else None
+            if taken:                     # once per geometry: later calls may come from other streams (the lanes of a pipelined pass)
+                torch.cuda.current_stream(x.device).synchronize()
+        return store[key]
 
     def _body_train_fused(self, x, sizes):
         """Branches + merge_layer.0/1/2 as one autograd node (autograd.PyrBodyFn); frozen BatchNorms only."""

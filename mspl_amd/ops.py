@@ -585,8 +585,37 @@ def pyr_down_prep(x, sizes, stage_ws, keep_pooled=False):
     return outs
 
 
-def pyrpool_fused(x, sizes, stage_ws, down_es, br_scale, br_shift, br_alpha, merge_w, ep=None, out=None):
-    """K6.  x (N,P,h,w); sizes: [(hs,ws)] per branch; stage_ws / down_es: per-branch tensors or None."""
+def pyrpool_stream_plan(shape, sizes):
+    """What the register-streaming form of K6 decides for an (N,P,h,w) map with these branch sizes (mspl_pyrpool_stream_plan, the
+    launcher's own host function): a dict taken / t0 / t1 / pxl / ncb / cbw / seg / nseg / waves / seg_inkernel / nseg_inkernel /
+    waves_inkernel, every value 0 when the shapes are left to the other forms."""
+    N, P, h, w = [int(v) for v in shape]
+    nb = len(sizes)
+    hs = (ctypes.c_int32 * nb)(*[int(s[0]) for s in sizes])
+    ws = (ctypes.c_int32 * nb)(*[int(s[1]) for s in sizes])
+    out = (ctypes.c_int32 * nat.PYR_STREAM_PLAN_LEN)()
+    check(lib.mspl_pyrpool_stream_plan(N, P, h, w, nb, hs, ws, out))
+    names = ('TAKEN', 'T0', 'T1', 'PXL', 'NCB', 'CBW', 'SEG', 'NSEG', 'WAVES', 'SEG_INKERNEL', 'NSEG_INKERNEL', 'WAVES_INKERNEL')
+    return {n.lower(): int(out[getattr(nat, 'PYR_STREAM_PLAN_' + n)]) for n in names}
+
+
+def pyr_stream_tables(h, w, sizes, device):
+    """The geometry tables of K6's streaming form for an h x w map with these branch sizes (a float32 tensor for pyrpool_fused's
+    `tables`), or None when that form does not cover the geometry.  One small launch on the current stream."""
+    nb = len(sizes)
+    hs = (ctypes.c_int32 * nb)(*[int(s[0]) for s in sizes])
+    ws = (ctypes.c_int32 * nb)(*[int(s[1]) for s in sizes])
+    nbytes = int(lib.mspl_pyr_stream_tables_bytes(int(h), int(w), nb, hs, ws))
+    if nbytes <= 0:
+        return None
+    tab = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+    check(lib.mspl_pyr_stream_tables_build(int(h), int(w), nb, hs, ws, _p(tab), nbytes, _stream()))
+    return tab
+
+
+def pyrpool_fused(x, sizes, stage_ws, down_es, br_scale, br_shift, br_alpha, merge_w, ep=None, out=None, tables=None):
+    """K6.  x (N,P,h,w); sizes: [(hs,ws)] per branch; stage_ws / down_es: per-branch tensors or None.  tables: what
+    pyr_stream_tables built for this geometry (same output bits, less work per launch), or None."""
     x = _f32(x, 'x')
     N, P, h, w = x.shape
     nb = len(sizes)
@@ -613,6 +642,11 @@ def pyrpool_fused(x, sizes, stage_ws, down_es, br_scale, br_shift, br_alpha, mer
     bs, bh, ba = _vec(br_scale, nb * P, 'br_scale'), _vec(br_shift, nb * P, 'br_shift'), _vec(br_alpha, nb * P, 'br_alpha')
     dst, coff = _dest(out, (N, P, h, w), x)
     s, k2 = _build(ep, dst, coff, N, P, h * w)
+    if tables is not None and not (s.pre_add or s.residual or s.reinf_r or s.gate or s.raw_out):   # (the streaming form's epilogue)
+        check(lib.mspl_pyrpool_fused_tab_fwd(_p(x), N, P, h, w, nb, hs, ws, sw, de, _p(bs), _p(bh), _p(ba), _p(merge_w),
+                                             s.scale, s.shift, s.alpha, s.out_ctot, s.out_coff, s.flags, _p(dst), _p(tables),
+                                             _stream()))
+        return dst
     check(lib.mspl_pyrpool_fused_fwd(_p(x), N, P, h, w, nb, hs, ws, sw, de, _p(bs), _p(bh), _p(ba), _p(merge_w),
                                      ctypes.byref(s), _p(dst), _stream()))
     return dst
