@@ -952,6 +952,26 @@ int mspl_train_transform_fwd(const uint8_t* rgb, const uint8_t* label, const uin
                              int32_t H, int32_t W, int32_t crop, int32_t ignore_idx, const mspl_train_rec_t* recs_host,
                              const mspl_train_rec_t* recs_dev, const float* mean, const float* stdv, uint8_t* ws, int32_t max_sh,
                              int32_t max_sw, float* out_rgb, int64_t* out_label, float* out_depth, void* stream);
+/* The same transforms reading a device-resident STORE by slot: rgb (M,Hs,Ws,3), label (M,Hl,Wl) or NULL, depth (M,Hs,Ws) or NULL.
+ * Output image n comes from slot slots[n]: slots_host / slots_dev are N int32 in the records' arrangement (host copy checked against
+ * [0, M) here -- MSPL_ERR_BAD_SHAPE, nothing launched --, device copy read by the kernels); a slot may repeat; both NULL: slot n = n
+ * (then N <= M).  Slot offsets are 64-bit: a store may exceed 4 GiB.  The label maps have their own size (Hl, Wl) and still reach
+ * the output by one gather:
+ *   scale_stage != 0 (the pipeline has a RandomScale): NEAREST (Hl,Wl) -> (sh,sw) as RandomScale resizes a label from its own size
+ *       (data_transforms.py:78-85), then NEAREST (sh,sw) -> (H,W) or pad + crop.  near_x / near_y: NEAREST Wl -> sw / Hl -> sh, needed
+ *       where sw != Wl / sh != Hl whether or not the frame itself is scaled; near_out_*: NEAREST sw -> W / sh -> H.
+ *   scale_stage == 0: every record has (sh,sw) = (Hs,Ws).  Resize: ONE NEAREST (Hl,Wl) -> (H,W) (data_transforms.py:191-212), not the
+ *       composition through (Hs,Ws): near_out_x / near_out_y are NEAREST Wl -> W / Hl -> H, near_x / near_y are not read.  Crop with
+ *       (Hl,Wl) != (Hs,Ws): MSPL_ERR_UNSUPPORTED (the reference would crop misaligned images).
+ * label_lut: 256 device bytes or NULL, applied to the SOURCE label values in the gather (the remaps datasets apply before their
+ * transforms: greenhouse.py:248-251, camvid.py:120-125); RandomCrop's pad fill ignore_idx does not pass through it.
+ * mspl_train_transform_fwd is this call with M = N, no slots, (Hl,Wl) = (Hs,Ws), scale_stage = 1 and no LUT. */
+int mspl_train_transform_store_fwd(const uint8_t* rgb, const uint8_t* label, const uint8_t* depth, int32_t M, int32_t N, int32_t Hs,
+                                   int32_t Ws, int32_t Hl, int32_t Wl, int32_t H, int32_t W, int32_t crop, int32_t scale_stage,
+                                   int32_t ignore_idx, const mspl_train_rec_t* recs_host, const mspl_train_rec_t* recs_dev,
+                                   const int32_t* slots_host, const int32_t* slots_dev, const uint8_t* label_lut, const float* mean,
+                                   const float* stdv, uint8_t* ws, int32_t max_sh, int32_t max_sw, float* out_rgb,
+                                   int64_t* out_label, float* out_depth, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,9 @@
 //       Writes the scaled uint8 image to the caller's workspace; images whose size does not change are skipped (read in place).
 //   output: Resize (the same fused tile, BILINEAR) or pad + crop, mirror, /255, normalise for rgb and depth, and the label as ONE
 //       gather through the composed NEAREST index tables -- one launch for all three outputs.
-// Every size and table entry is clamped where it is used: a bad record gives wrong pixels, never an access outside the buffers.
+// The inputs are STORES of M frames read by slot (mspl_train_transform_store_fwd; a contiguous batch is the store of N slots read in
+// order), the label maps have their own size (Hl, Wl), and a 256-byte table may remap the source label values inside the gather.
+// Every size, slot and table entry is clamped where it is used: a bad record gives wrong pixels, never an access outside the buffers.
 #include <algorithm>
 #include <cmath>
 
@@ -132,8 +134,15 @@ __device__ __forceinline__ void resample_tile(const uint8_t* __restrict__ img, i
 
 __device__ __forceinline__ bool rec_scaled(const mspl_train_rec_t& r, int Hs, int Ws) { return r.sh != Hs || r.sw != Ws; }
 
+// Image n of the batch is slot slots[n] of the store (n itself without a slot list), clamped into the store.
+__device__ __forceinline__ size_t slot_of(const int32_t* __restrict__ slots, int n, int M) {
+    return (size_t)clampi(slots ? slots[n] : n, 0, M - 1);
+}
+
 struct ScaleArgs {
-    const uint8_t* src;            // (N,Hs,Ws,C)
+    const uint8_t* src;            // store (M,Hs,Ws,C)
+    const int32_t* slots;          // N slot numbers or null
+    int M;
     const mspl_train_rec_t* recs;
     uint8_t* ws;                   // (N, max_sh * max_sw * C)
     int Hs, Ws, max_sh, max_sw, rows_cap, depth;
@@ -150,7 +159,7 @@ __global__ __launch_bounds__(TT_THREADS) void train_scale_kernel(ScaleArgs a) {
     if (!rec_scaled(r, a.Hs, a.Ws) || oy0 >= sh || ox0 >= sw) return;        // whole workgroup: before any barrier
     const int32_t* xt = sw != a.Ws ? (a.depth ? r.dscale_x : r.scale_x) : nullptr;
     const int32_t* yt = sh != a.Hs ? (a.depth ? r.dscale_y : r.scale_y) : nullptr;
-    const uint8_t* img = a.src + (size_t)n * a.Hs * a.Ws * C;
+    const uint8_t* img = a.src + slot_of(a.slots, n, a.M) * a.Hs * a.Ws * C;
     uint8_t* dst = a.ws + (size_t)n * a.max_sh * a.max_sw * C;
     resample_tile<C>(img, a.Hs, a.Ws, sh, sw, xt, yt, oy0, ox0, a.rows_cap, hbuf, [&](int yo, int xo, uint32_t px) {
         uint8_t* d = dst + ((size_t)yo * sw + xo) * C;
@@ -160,9 +169,11 @@ __global__ __launch_bounds__(TT_THREADS) void train_scale_kernel(ScaleArgs a) {
 }
 
 struct OutArgs {
-    const uint8_t* rgb;            // (N,Hs,Ws,3)
-    const uint8_t* label;          // (N,Hs,Ws) or null
-    const uint8_t* depth;          // (N,Hs,Ws) or null
+    const uint8_t* rgb;            // store (M,Hs,Ws,3)
+    const uint8_t* label;          // store (M,Hl,Wl) or null
+    const uint8_t* depth;          // store (M,Hs,Ws) or null
+    const int32_t* slots;          // N slot numbers or null
+    const uint8_t* lut;            // 256 bytes: remap of the source label values, or null
     const mspl_train_rec_t* recs;
     const uint8_t* ws_rgb;         // scaled rgb, (N, max_sh * max_sw * 3)
     const uint8_t* ws_depth;       // scaled depth, (N, max_sh * max_sw)
@@ -171,7 +182,7 @@ struct OutArgs {
     float* out_rgb;                // (N,3,H,W)
     int64_t* out_label;            // (N,H,W)
     float* out_depth;              // (N,1,H,W)
-    int Hs, Ws, H, W, max_sh, max_sw, crop, ignore_idx, rows_cap;
+    int M, Hs, Ws, Hl, Wl, H, W, max_sh, max_sw, crop, scale_stage, ignore_idx, rows_cap;
 };
 
 // Pad + crop: output (yo, xo) is pixel (yo + dy, xo + dx) of the sh x sw image, 0 (the Pad fill) outside it.
@@ -203,9 +214,10 @@ __global__ __launch_bounds__(TT_THREADS) void train_output_kernel(OutArgs a) {
     const int32_t* xt = (!a.crop && sw != W) ? r.out_x : nullptr;
     const int32_t* yt = (!a.crop && sh != H) ? r.out_y : nullptr;
     const size_t plane = (size_t)H * W;
+    const size_t slot = slot_of(a.slots, n, a.M);
 
     {   // rgb
-        const uint8_t* img = scaled ? a.ws_rgb + (size_t)n * a.max_sh * a.max_sw * 3 : a.rgb + (size_t)n * a.Hs * a.Ws * 3;
+        const uint8_t* img = scaled ? a.ws_rgb + (size_t)n * a.max_sh * a.max_sw * 3 : a.rgb + slot * a.Hs * a.Ws * 3;
         float* o = a.out_rgb + (size_t)n * 3 * plane;
         float m[3] = {0.f, 0.f, 0.f}, s[3] = {1.f, 1.f, 1.f};
         const bool norm = a.mean != nullptr;
@@ -227,7 +239,7 @@ __global__ __launch_bounds__(TT_THREADS) void train_output_kernel(OutArgs a) {
     }
     if (a.out_depth) {
         __syncthreads();                                                  // hbuf is reused
-        const uint8_t* img = scaled ? a.ws_depth + (size_t)n * a.max_sh * a.max_sw : a.depth + (size_t)n * a.Hs * a.Ws;
+        const uint8_t* img = scaled ? a.ws_depth + (size_t)n * a.max_sh * a.max_sw : a.depth + slot * a.Hs * a.Ws;
         float* o = a.out_depth + (size_t)n * plane;
         auto emit = [&](int yo, int xo, uint32_t px) {
             const int xd = flip ? W - 1 - xo : xo;
@@ -237,12 +249,15 @@ __global__ __launch_bounds__(TT_THREADS) void train_output_kernel(OutArgs a) {
         else resample_tile<1>(img, sh, sw, H, W, xt, yt, oy0, ox0, a.rows_cap, hbuf, emit);
     }
     if (a.out_label) {   // NEAREST (scale) then NEAREST (Resize) or pad + crop, composed into one gather from the source map
-        const uint8_t* lab = a.label + (size_t)n * a.Hs * a.Ws;
+        // The map has its own size (Hl, Wl).  RandomScale resizes it from that size to the frame's scaled size (lsh, lsw) = (sh, sw);
+        // without that stage it reaches Resize as it is: (lsh, lsw) = (Hl, Wl).
+        const int lsh = a.scale_stage ? sh : a.Hl, lsw = a.scale_stage ? sw : a.Wl;
+        const uint8_t* lab = a.label + slot * a.Hl * a.Wl;
         int64_t* o = a.out_label + (size_t)n * plane;
-        const int32_t* nx = sw != a.Ws ? r.near_x : nullptr;
-        const int32_t* ny = sh != a.Hs ? r.near_y : nullptr;
-        const int32_t* nox = (!a.crop && sw != W) ? r.near_out_x : nullptr;
-        const int32_t* noy = (!a.crop && sh != H) ? r.near_out_y : nullptr;
+        const int32_t* nx = lsw != a.Wl ? r.near_x : nullptr;
+        const int32_t* ny = lsh != a.Hl ? r.near_y : nullptr;
+        const int32_t* nox = (!a.crop && lsw != W) ? r.near_out_x : nullptr;
+        const int32_t* noy = (!a.crop && lsh != H) ? r.near_out_y : nullptr;
         for (int i = threadIdx.x; i < TT_H * TT_W; i += TT_THREADS) {
             const int yl = i / TT_W, xl = i - yl * TT_W;
             const int yo = oy0 + yl, xo = ox0 + xl;
@@ -256,10 +271,11 @@ __global__ __launch_bounds__(TT_THREADS) void train_output_kernel(OutArgs a) {
                 xx = nox ? nox[xo] : xo;
             }
             int64_t v = a.ignore_idx;
-            if (yy >= 0 && yy < sh && xx >= 0 && xx < sw) {
-                const int ry = clampi(ny ? ny[yy] : yy, 0, a.Hs - 1);
-                const int rx = clampi(nx ? nx[xx] : xx, 0, a.Ws - 1);
-                v = lab[(size_t)ry * a.Ws + rx];
+            if (yy >= 0 && yy < lsh && xx >= 0 && xx < lsw) {
+                const int ry = clampi(ny ? ny[yy] : yy, 0, a.Hl - 1);
+                const int rx = clampi(nx ? nx[xx] : xx, 0, a.Wl - 1);
+                const uint8_t sv = lab[(size_t)ry * a.Wl + rx];
+                v = a.lut ? a.lut[sv] : sv;                               // the pad fill above does not pass through the remap
             }
             o[(size_t)yo * W + (flip ? W - 1 - xo : xo)] = v;
         }
@@ -286,11 +302,13 @@ extern "C" int64_t mspl_train_transform_workspace_bytes(int32_t N, int32_t max_s
     return (int64_t)N * max_sh * max_sw * (with_depth ? 4 : 3);
 }
 
-extern "C" int mspl_train_transform_fwd(const uint8_t* rgb, const uint8_t* label, const uint8_t* depth, int32_t N, int32_t Hs,
-                                        int32_t Ws, int32_t H, int32_t W, int32_t crop, int32_t ignore_idx,
-                                        const mspl_train_rec_t* recs_host, const mspl_train_rec_t* recs_dev, const float* mean,
-                                        const float* stdv, uint8_t* ws, int32_t max_sh, int32_t max_sw, float* out_rgb,
-                                        int64_t* out_label, float* out_depth, void* stream) {
+extern "C" int mspl_train_transform_store_fwd(const uint8_t* rgb, const uint8_t* label, const uint8_t* depth, int32_t M, int32_t N,
+                                              int32_t Hs, int32_t Ws, int32_t Hl, int32_t Wl, int32_t H, int32_t W, int32_t crop,
+                                              int32_t scale_stage, int32_t ignore_idx, const mspl_train_rec_t* recs_host,
+                                              const mspl_train_rec_t* recs_dev, const int32_t* slots_host, const int32_t* slots_dev,
+                                              const uint8_t* label_lut, const float* mean, const float* stdv, uint8_t* ws,
+                                              int32_t max_sh, int32_t max_sw, float* out_rgb, int64_t* out_label, float* out_depth,
+                                              void* stream) {
     MSPL_REQUIRE(rgb && recs_host && recs_dev && out_rgb, MSPL_ERR_NULL_POINTER, "train_transform: null pointer");
     MSPL_REQUIRE(N > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0 && max_sh > 0 && max_sw > 0, MSPL_ERR_BAD_SHAPE,
                  "train_transform: bad shape N=%d %dx%d -> %dx%d (scaled at most %dx%d)", N, Hs, Ws, H, W, max_sh, max_sw);
@@ -300,6 +318,18 @@ extern "C" int mspl_train_transform_fwd(const uint8_t* rgb, const uint8_t* label
                  "train_transform: label / depth and their outputs go together");
     MSPL_REQUIRE((mean == nullptr) == (stdv == nullptr), MSPL_ERR_NULL_POINTER, "train_transform: mean and std go together");
     MSPL_REQUIRE(ignore_idx >= -0x7fffffff, MSPL_ERR_BAD_SHAPE, "train_transform: ignore_idx");
+    MSPL_REQUIRE(M > 0 && (slots_host == nullptr) == (slots_dev == nullptr), MSPL_ERR_BAD_SHAPE,
+                 "train_transform: a store of %d slots, or one slot list without its copy", M);
+    MSPL_REQUIRE(slots_host || N <= M, MSPL_ERR_BAD_SHAPE, "train_transform: %d images from a store of %d slots", N, M);
+    for (int n = 0; slots_host && n < N; ++n)
+        MSPL_REQUIRE(slots_host[n] >= 0 && slots_host[n] < M, MSPL_ERR_BAD_SHAPE, "train_transform: image %d reads slot %d of a store of %d",
+                     n, slots_host[n], M);
+    if (label) {
+        MSPL_REQUIRE(Hl > 0 && Wl > 0 && (int64_t)Hl * Wl <= 0x7fffffff, MSPL_ERR_BAD_SHAPE, "train_transform: label maps of %dx%d", Hl, Wl);
+        MSPL_REQUIRE(scale_stage || !crop || (Hl == Hs && Wl == Ws), MSPL_ERR_UNSUPPORTED,
+                     "train_transform: RandomCrop without RandomScale of %dx%d label maps on %dx%d frames (the reference crops them "
+                     "misaligned)", Hl, Wl, Hs, Ws);
+    }
     int scale_rows = 1, dscale_rows = 1, out_rows = 1, sh_max = 0, sw_max = 0;
     bool any_scaled = false;
     for (int n = 0; n < N; ++n) {
@@ -308,10 +338,14 @@ extern "C" int mspl_train_transform_fwd(const uint8_t* rgb, const uint8_t* label
                      "train_transform: image %d scaled to %dx%d, outside 1..%dx%d", n, r.sh, r.sw, max_sh, max_sw);
         MSPL_REQUIRE(r.flip == 0 || r.flip == 1, MSPL_ERR_BAD_SHAPE, "train_transform: image %d flip %d", n, r.flip);
         const bool sx = r.sw != Ws, sy = r.sh != Hs;
+        MSPL_REQUIRE(scale_stage || !(sx || sy), MSPL_ERR_BAD_SHAPE, "train_transform: image %d scaled to %dx%d without a RandomScale stage",
+                     n, r.sh, r.sw);
         MSPL_REQUIRE((!sx || r.scale_x) && (!sy || r.scale_y), MSPL_ERR_NULL_POINTER, "train_transform: image %d scale tables", n);
         MSPL_REQUIRE(!depth || ((!sx || r.dscale_x) && (!sy || r.dscale_y)), MSPL_ERR_NULL_POINTER,
                      "train_transform: image %d depth scale tables", n);
-        MSPL_REQUIRE(!label || ((!sx || r.near_x) && (!sy || r.near_y)), MSPL_ERR_NULL_POINTER,
+        // the label map goes from its own size to (lsh, lsw): the frame's scaled size, or its own size without a RandomScale stage
+        const int lsh = scale_stage ? r.sh : Hl, lsw = scale_stage ? r.sw : Wl;
+        MSPL_REQUIRE(!label || ((lsw == Wl || r.near_x) && (lsh == Hl || r.near_y)), MSPL_ERR_NULL_POINTER,
                      "train_transform: image %d label scale tables", n);
         if (crop) {
             MSPL_REQUIRE(r.pad_h >= 0 && r.pad_w >= 0 && r.sh + 2 * r.pad_h >= H && r.sw + 2 * r.pad_w >= W, MSPL_ERR_BAD_SHAPE,
@@ -323,7 +357,7 @@ extern "C" int mspl_train_transform_fwd(const uint8_t* rgb, const uint8_t* label
         } else {
             MSPL_REQUIRE((r.sw == W || r.out_x) && (r.sh == H || r.out_y), MSPL_ERR_NULL_POINTER,
                          "train_transform: image %d Resize tables", n);
-            MSPL_REQUIRE(!label || ((r.sw == W || r.near_out_x) && (r.sh == H || r.near_out_y)), MSPL_ERR_NULL_POINTER,
+            MSPL_REQUIRE(!label || ((lsw == W || r.near_out_x) && (lsh == H || r.near_out_y)), MSPL_ERR_NULL_POINTER,
                          "train_transform: image %d label Resize tables", n);
             out_rows = std::max(out_rows, tile_rows(r.sh, H, 1.0));
         }
@@ -341,20 +375,31 @@ extern "C" int mspl_train_transform_fwd(const uint8_t* rgb, const uint8_t* label
                  TT_MAX_ROWS);
     hipStream_t s = (hipStream_t)stream;
     if (any_scaled) {
-        ScaleArgs sa{rgb, recs_dev, ws, Hs, Ws, max_sh, max_sw, scale_rows, 0};
+        ScaleArgs sa{rgb, slots_dev, M, recs_dev, ws, Hs, Ws, max_sh, max_sw, scale_rows, 0};
         dim3 grid((unsigned)ceil_div(sw_max, TT_W), (unsigned)ceil_div(sh_max, TT_H), (unsigned)N);
         hipLaunchKernelGGL(train_scale_kernel<3>, grid, dim3(TT_THREADS), (size_t)scale_rows * TT_W * 4, s, sa);
         MSPL_CHECK_LAUNCH("train_transform(scale rgb)");
         if (depth) {
-            ScaleArgs da{depth, recs_dev, ws + (size_t)N * max_sh * max_sw * 3, Hs, Ws, max_sh, max_sw, dscale_rows, 1};
+            ScaleArgs da{depth, slots_dev, M, recs_dev, ws + (size_t)N * max_sh * max_sw * 3, Hs, Ws, max_sh, max_sw, dscale_rows, 1};
             hipLaunchKernelGGL(train_scale_kernel<1>, grid, dim3(TT_THREADS), (size_t)dscale_rows * TT_W * 4, s, da);
             MSPL_CHECK_LAUNCH("train_transform(scale depth)");
         }
     }
-    OutArgs oa{rgb, label, depth, recs_dev, ws, ws ? ws + (size_t)N * max_sh * max_sw * 3 : nullptr, mean, stdv, out_rgb, out_label,
-               out_depth, Hs, Ws, H, W, max_sh, max_sw, crop ? 1 : 0, ignore_idx, out_rows};
+    OutArgs oa{rgb, label, depth, slots_dev, label ? label_lut : nullptr, recs_dev, ws, ws ? ws + (size_t)N * max_sh * max_sw * 3 : nullptr,
+               mean, stdv, out_rgb, out_label, out_depth, M, Hs, Ws, label ? Hl : Hs, label ? Wl : Ws, H, W, max_sh, max_sw,
+               crop ? 1 : 0, scale_stage ? 1 : 0, ignore_idx, out_rows};
     dim3 grid((unsigned)ceil_div(W, TT_W), (unsigned)ceil_div(H, TT_H), (unsigned)N);
     hipLaunchKernelGGL(train_output_kernel, grid, dim3(TT_THREADS), crop ? 0 : (size_t)out_rows * TT_W * 4, s, oa);
     MSPL_CHECK_LAUNCH("train_transform(output)");
     return MSPL_OK;
+}
+
+// A contiguous batch is a store of N slots read in order, its label maps at the frame's size; the records alone say what is scaled.
+extern "C" int mspl_train_transform_fwd(const uint8_t* rgb, const uint8_t* label, const uint8_t* depth, int32_t N, int32_t Hs,
+                                        int32_t Ws, int32_t H, int32_t W, int32_t crop, int32_t ignore_idx,
+                                        const mspl_train_rec_t* recs_host, const mspl_train_rec_t* recs_dev, const float* mean,
+                                        const float* stdv, uint8_t* ws, int32_t max_sh, int32_t max_sw, float* out_rgb,
+                                        int64_t* out_label, float* out_depth, void* stream) {
+    return mspl_train_transform_store_fwd(rgb, label, depth, N, N, Hs, Ws, Hs, Ws, H, W, crop, 1, ignore_idx, recs_host, recs_dev, nullptr,
+                                          nullptr, nullptr, mean, stdv, ws, max_sh, max_sw, out_rgb, out_label, out_depth, stream);
 }

@@ -13,8 +13,13 @@ go to the device as they are (3 B/pixel instead of 12) and `Preprocessor` does R
 launches with Pillow's exact fixed-point arithmetic; `LabelWriter` copies the merged uint8 maps back on a side stream into
 pinned memory and native worker threads (C++ + zlib inside the library) encode/write the PNGs while the next batch is on the GPU.  Decoding the source JPEG /
 PNG files stays with PIL on the host (file formats are outside the path).
+
+The target set of a self-training run is static and only its labels change: `FrameStore` holds the decoded uint8 frames on the
+device for the whole run, the label loops write their maps into it (`label_sink=store.put_labels`) and `ResidentTrainLoader` yields
+the reference dataset's train batches from it (shuffled slots, `TrainPreprocessor` reading the store in place).
 """
 import collections
+import contextlib
 import ctypes
 import math
 import os
@@ -194,8 +199,8 @@ class TrainPreprocessor(object):
 
     (CamVid's Resize after its RandomCrop is Pillow's copy path: the crop is the size.)  `draw()` makes the reference's random draws
     with its own calls in its order; `__call__` uploads the per-image records (112 bytes each, pinned, asynchronous) and runs at most
-    three launches.  Label remaps that datasets apply before their transforms (camvid.py:120-125, greenhouse.py:248-251) and image
-    decoding stay with the caller."""
+    three launches.  Label remaps that datasets apply before their transforms (camvid.py:120-125, greenhouse.py:248-251) go in as
+    `label_lut` or stay with the caller; image decoding stays with the caller (FrameStore.from_list does it once per run)."""
 
     def __init__(self, size=(480, 256), scale=(0.5, 2.0), crop=False, ignore_idx=255, normalize=True, device='cuda'):
         self.size = size if isinstance(size, tuple) else (size, size)
@@ -262,7 +267,9 @@ class TrainPreprocessor(object):
             self._tables[key] = torch.from_numpy(idx).to(self.device)
         return self._tables[key].data_ptr()
 
-    def _record(self, p, Hs, Ws, with_label, with_depth):
+    def _record(self, p, Hs, Ws, label_size, with_depth, scale_stage=True):
+        """label_size: (Hl, Wl) of the label maps or None.  The label goes from its own size to (lsh, lsw) -- the frame's scaled size
+        with a RandomScale stage (data_transforms.py:78-85), its own size without one -- and from there to the output."""
         W, H = self.size
         r = TrainRec()
         r.sh, r.sw, r.pad_h, r.pad_w, r.crop_i, r.crop_j, r.flip = p.sh, p.sw, p.pad_h, p.pad_w, p.i, p.j, int(bool(p.flip))
@@ -271,18 +278,26 @@ class TrainPreprocessor(object):
         if p.sw != Ws:
             r.scale_x = self._resample_table(Ws, p.sw, FILTER_LANCZOS)
             r.dscale_x = self._resample_table(Ws, p.sw, FILTER_BILINEAR) if with_depth else None
-            r.near_x = self._nearest_table(Ws, p.sw) if with_label else None
         if p.sh != Hs:
             r.scale_y = self._resample_table(Hs, p.sh, FILTER_LANCZOS)
             r.dscale_y = self._resample_table(Hs, p.sh, FILTER_BILINEAR) if with_depth else None
-            r.near_y = self._nearest_table(Hs, p.sh) if with_label else None
         if not self.crop:
             if p.sw != W:
                 r.out_x = self._resample_table(p.sw, W, FILTER_BILINEAR)
-                r.near_out_x = self._nearest_table(p.sw, W) if with_label else None
             if p.sh != H:
                 r.out_y = self._resample_table(p.sh, H, FILTER_BILINEAR)
-                r.near_out_y = self._nearest_table(p.sh, H) if with_label else None
+        if label_size is not None:
+            Hl, Wl = label_size
+            lsh, lsw = (p.sh, p.sw) if scale_stage else (Hl, Wl)
+            if lsw != Wl:
+                r.near_x = self._nearest_table(Wl, lsw)
+            if lsh != Hl:
+                r.near_y = self._nearest_table(Hl, lsh)
+            if not self.crop:
+                if lsw != W:
+                    r.near_out_x = self._nearest_table(lsw, W)
+                if lsh != H:
+                    r.near_out_y = self._nearest_table(lsh, H)
         return r
 
     def _up(self, t, name, ndim):
@@ -301,29 +316,47 @@ class TrainPreprocessor(object):
                                % (name, dtype, shape, t.dtype, tuple(t.shape)))
         return t
 
-    def __call__(self, rgb, label=None, depth=None, params=None, out=None):
-        """rgb (N,Hs,Ws,3), label (N,Hs,Ws), depth (N,Hs,Ws): uint8, host or device.  params: N records from draw() (None: draw()
+    def __call__(self, rgb, label=None, depth=None, params=None, out=None, slots=None, label_lut=None):
+        """rgb (N,Hs,Ws,3), label (N,Hl,Wl), depth (N,Hs,Ws): uint8, host or device.  params: N records from draw() (None: draw()
         with the module-level `random`, as the reference's dataset does).  out: destination tensors -- the image tensor, or a tuple
         (x, y, d) whose entries may be None -- e.g. a train step's static input buffers.  Returns (x (N,3,H,W) fp32, y (N,H,W) int64
-        | None, d (N,1,H,W) fp32 | None) on the device."""
+        | None, d (N,1,H,W) fp32 | None) on the device.
+
+        The label maps may have a size of their own: RandomScale resizes them from it to the frame's scaled size
+        (data_transforms.py:78-85), and a pipeline without RandomScale resizes them from it to `size` in one step (:191-212; with
+        crop=True that case is refused: the reference would crop misaligned images).  slots: N slot numbers (a sequence or an int
+        tensor on the host; a slot may repeat) -- the first three arguments are then STORES of M >= 1 frames (FrameStore.rgb /
+        .labels / .depth) and output n comes from slot slots[n]: no staging copy.  label_lut: 256 uint8 values remapping the
+        SOURCE label values in the gather (greenhouse.py:248-251, camvid.py:120-125); RandomCrop's fill is not remapped."""
         rgb = self._up(rgb, 'rgb', 4)
         if rgb.shape[3] != 3:
             raise RuntimeError('mspl_amd: rgb must be (N,H,W,3) uint8, got %s' % (tuple(rgb.shape),))
-        N, Hs, Ws = rgb.shape[:3]
+        M, Hs, Ws = rgb.shape[:3]
+        if slots is None:
+            N, slot_list = M, None
+        else:
+            slot_list = [int(v) for v in (slots.tolist() if hasattr(slots, 'tolist') else slots)]
+            N = len(slot_list)
+            if N == 0:
+                raise RuntimeError('mspl_amd: TrainPreprocessor: an empty slot list')
+        label_size = None
         if label is not None:
             label = self._up(label, 'label', 3)
-            if tuple(label.shape) != (N, Hs, Ws):
-                raise RuntimeError('mspl_amd: label shape %s does not match the image batch %s' % (tuple(label.shape), (N, Hs, Ws)))
+            if label.shape[0] != M or 0 in label.shape:
+                raise RuntimeError('mspl_amd: label shape %s does not match the image batch %s' % (tuple(label.shape), (M, Hs, Ws)))
+            label_size = tuple(label.shape[1:])
         if depth is not None:
             depth = self._up(depth, 'depth', 3)
-            if tuple(depth.shape) != (N, Hs, Ws):
-                raise RuntimeError('mspl_amd: depth shape %s does not match the image batch %s' % (tuple(depth.shape), (N, Hs, Ws)))
+            if tuple(depth.shape) != (M, Hs, Ws):
+                raise RuntimeError('mspl_amd: depth shape %s does not match the image batch %s' % (tuple(depth.shape), (M, Hs, Ws)))
         if params is None:
             params = self.draw(N, (Ws, Hs))
         if len(params) != N:
             raise RuntimeError('mspl_amd: %d records for a batch of %d images' % (len(params), N))
         W, H = self.size
-        recs = (TrainRec * N)(*[self._record(p, Hs, Ws, label is not None, depth is not None) for p in params])
+        # label maps of the frame's size: the records alone say what is scaled, as they always have
+        scale_stage = self.scale is not None or label_size in (None, (Hs, Ws))
+        recs = (TrainRec * N)(*[self._record(p, Hs, Ws, label_size, depth is not None, scale_stage) for p in params])
         scaled = [(p.sh, p.sw) for p in params if (p.sh, p.sw) != (Hs, Ws)]
         ws = None
         if scaled:
@@ -348,15 +381,275 @@ class TrainPreprocessor(object):
         if self.normalize and self._mean is None:
             self._mean = torch.tensor(MEAN, dtype=torch.float32, device=self.device)
             self._std = torch.tensor(STD, dtype=torch.float32, device=self.device)
-        host = torch.empty(ctypes.sizeof(recs), dtype=torch.uint8, pin_memory=True)
-        ctypes.memmove(host.data_ptr(), ctypes.addressof(recs), ctypes.sizeof(recs))
+        if label_lut is not None:
+            label_lut = torch.as_tensor(label_lut)
+            if label_lut.dtype != torch.uint8 or label_lut.numel() != 256:
+                raise RuntimeError('mspl_amd: label_lut must hold 256 uint8 values, got %s %s' % (label_lut.dtype, tuple(label_lut.shape)))
+            label_lut = label_lut.to(self.device, non_blocking=True).contiguous()
+        # one pinned block, one copy: the records, then the slot numbers (the records are 112 bytes each: int32 alignment holds)
+        nrec = ctypes.sizeof(recs)
+        host = torch.empty(nrec + (4 * N if slot_list is not None else 0), dtype=torch.uint8, pin_memory=True)
+        ctypes.memmove(host.data_ptr(), ctypes.addressof(recs), nrec)
+        if slot_list is not None:
+            if min(slot_list) < -2 ** 31 or max(slot_list) >= 2 ** 31:     # the library checks [0, M); nothing may wrap before it
+                raise RuntimeError('mspl_amd: TrainPreprocessor: slot numbers must fit int32')
+            host[nrec:].view(torch.int32).copy_(torch.tensor(slot_list, dtype=torch.int32))
         dev = host.to(self.device, non_blocking=True)              # the allocator keeps `host` until the copy has run
         p = lambda t: None if t is None else t.data_ptr()
-        check(lib.mspl_train_transform_fwd(rgb.data_ptr(), p(label), p(depth), N, Hs, Ws, H, W, int(self.crop), self.ignore_idx,
-                                           ctypes.addressof(recs), dev.data_ptr(), p(self._mean if self.normalize else None),
-                                           p(self._std if self.normalize else None), p(ws), max_sh, max_sw, x.data_ptr(), p(y), p(d),
-                                           torch.cuda.current_stream(self.device).cuda_stream))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        mean, std = (self._mean, self._std) if self.normalize else (None, None)
+        if slot_list is None and label_lut is None and label_size in (None, (Hs, Ws)):
+            check(lib.mspl_train_transform_fwd(rgb.data_ptr(), p(label), p(depth), N, Hs, Ws, H, W, int(self.crop), self.ignore_idx,
+                                               ctypes.addressof(recs), dev.data_ptr(), p(mean), p(std), p(ws), max_sh, max_sw,
+                                               x.data_ptr(), p(y), p(d), stream))
+            return x, y, d
+        Hl, Wl = label_size if label_size is not None else (Hs, Ws)
+        sh_ptr, sd_ptr = (host.data_ptr() + nrec, dev.data_ptr() + nrec) if slot_list is not None else (None, None)
+        check(lib.mspl_train_transform_store_fwd(rgb.data_ptr(), p(label), p(depth), M, N, Hs, Ws, Hl, Wl, H, W, int(self.crop),
+                                                 int(scale_stage), self.ignore_idx, ctypes.addressof(recs), dev.data_ptr(), sh_ptr, sd_ptr,
+                                                 p(label_lut), p(mean), p(std), p(ws), max_sh, max_sw, x.data_ptr(), p(y), p(d), stream))
         return x, y, d
+
+
+# ------------------------------------------------------------------ device-resident target set
+def _decode_depth_u8(path):
+    """The depth map as the reference's dataset reads it: cv2.imread(path, cv2.IMREAD_GRAYSCALE) (greenhouse.py:239).  Without OpenCV,
+    8-bit single-channel files go through Pillow (the same bytes); any other file needs OpenCV's conversion and is refused."""
+    try:
+        import cv2
+    except ImportError:
+        cv2 = None
+    if cv2 is not None:
+        a = cv2.imread(path, cv2.IMREAD_GRAYSCALE)
+        if a is None:
+            raise RuntimeError('mspl_amd: FrameStore: OpenCV could not read the depth map %s' % path)
+        return np.ascontiguousarray(a, dtype=np.uint8)
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode != 'L':
+            raise RuntimeError('mspl_amd: FrameStore: depth map %s has Pillow mode %r: without OpenCV (cv2) only 8-bit single-channel '
+                               'files are read as the reference reads them' % (path, im.mode))
+        return np.array(im, np.uint8)
+
+
+class _StoreFrames(object):
+    """FrameStore.frames(): consecutive slots as the tuples the label loop reads."""
+
+    def __init__(self, store, batch_size):
+        self.store, self.batch_size = store, int(batch_size)
+        if self.batch_size <= 0:
+            raise ValueError('mspl_amd: FrameStore.frames: batch_size %r' % (batch_size,))
+
+    def __len__(self):
+        return (len(self.store) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        s = self.store
+        for a in range(0, len(s), self.batch_size):
+            b = min(a + self.batch_size, len(s))
+            if s.depth is not None:
+                yield s.rgb[a:b], None, s.depth[a:b], s.names[a:b], None
+            else:
+                yield s.rgb[a:b], None, s.names[a:b], None
+
+
+class FrameStore(object):
+    """The decoded target set, held on the device for the whole run: the frames are static across the self-training
+    rounds and only their labels change, so they are decoded once and every epoch of every round reads them in place.
+
+        rgb     (M,Hs,Ws,3) uint8
+        labels  (M,Hl,Wl) uint8, or None until the first labels arrive (from_list(with_labels=True), from_arrays, put_labels)
+        depth   (M,Hs,Ws) uint8 or None
+        names   the image paths, exactly as in the list file
+
+    `frames(batch_size)` feeds the label pass, `put_labels` is its `label_sink`, ResidentTrainLoader trains from the store."""
+
+    def __init__(self, rgb, labels=None, depth=None, names=None):
+        M = rgb.shape[0]
+        self.rgb, self.labels, self.depth = rgb, labels, depth
+        self.names = [str(n) for n in names] if names is not None else ['%d' % k for k in range(M)]
+        if len(self.names) != M:
+            raise RuntimeError('mspl_amd: FrameStore: %d names for %d frames' % (len(self.names), M))
+        self._slots = {}
+        for k, n in enumerate(self.names):
+            self._slots.setdefault(n, []).append(k)
+        self.labelled = np.full(M, labels is not None, bool)       # host-side: which slots have received a label map
+
+    def __len__(self):
+        return self.rgb.shape[0]
+
+    @property
+    def device(self):
+        return self.rgb.device
+
+    def nbytes(self):
+        return sum(t.numel() for t in (self.rgb, self.labels, self.depth) if t is not None)
+
+    @staticmethod
+    def _as_u8(t, name, shape_tail, M=None):
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(t))
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 + len(shape_tail):
+            raise RuntimeError('mspl_amd: FrameStore: %s must be a uint8 array with %d dims, got %s %s'
+                               % (name, 1 + len(shape_tail), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        if (M is not None and t.shape[0] != M) or any(w is not None and w != g for w, g in zip(shape_tail, t.shape[1:])):
+            raise RuntimeError('mspl_amd: FrameStore: %s has shape %s, expected (%s, %s)'
+                               % (name, tuple(t.shape), 'M' if M is None else M, ', '.join('*' if w is None else str(w) for w in shape_tail)))
+        return t
+
+    @classmethod
+    def from_arrays(cls, rgb, labels=None, depth=None, names=None, device='cuda'):
+        """For callers with their own decoder: rgb (M,Hs,Ws,3), labels (M,Hl,Wl), depth (M,Hs,Ws) uint8 arrays or tensors."""
+        rgb = cls._as_u8(rgb, 'rgb', (None, None, 3))
+        M, Hs, Ws = rgb.shape[:3]
+        if M == 0:
+            raise RuntimeError('mspl_amd: FrameStore: no frames')
+        labels = None if labels is None else cls._as_u8(labels, 'labels', (None, None), M)
+        depth = None if depth is None else cls._as_u8(depth, 'depth', (Hs, Ws), M)
+        up = lambda t: None if t is None else t.to(device).contiguous()
+        return cls(up(rgb), up(labels), up(depth), names)
+
+    @classmethod
+    def from_list(cls, list_file, use_depth=False, with_labels=True, root=None, max_bytes=8 << 30, workers=None, device='cuda'):
+        """Decode the `image,label[,depth]` list once (read_image_list; greenhouse.py:232-245: frames `Image.open(p).convert('RGB')`,
+        labels `np.array(Image.open(p), np.uint8)`, depth as _decode_depth_u8) on at most min(16, host_cores()) threads and upload.
+        Every file must have the size of the first of its kind.  max_bytes: the device budget -- a larger set raises before anything
+        is allocated there.  Dataset label remaps (greenhouse.py:248-251) are not applied here: pass them as ResidentTrainLoader's
+        label_lut."""
+        from concurrent.futures import ThreadPoolExecutor
+        from PIL import Image
+        images, masks, depths = read_image_list(list_file, use_depth=use_depth, root=root, check_files=False)
+        for kind, paths in (('image', images), ('label', masks if with_labels else []), ('depth', depths)):
+            for p in paths:
+                if not os.path.isfile(p):
+                    raise FileNotFoundError('mspl_amd: FrameStore: %s file not found : %s' % (kind, p))
+        M = len(images)
+        if M == 0:
+            raise RuntimeError('mspl_amd: FrameStore: %s lists no images' % list_file)
+
+        def size_of(p):                                             # header only
+            with Image.open(p) as im:
+                return im.size[1], im.size[0]
+        Hs, Ws = size_of(images[0])
+        Hl, Wl = size_of(masks[0]) if with_labels else (0, 0)
+        need = M * (Hs * Ws * (4 if use_depth else 3) + Hl * Wl)
+        if need > max_bytes:
+            raise RuntimeError('mspl_amd: FrameStore: %d frames of %dx%d need %d bytes on the device, max_bytes is %d'
+                               % (M, Ws, Hs, need, max_bytes))
+        rgb = np.empty((M, Hs, Ws, 3), np.uint8)
+        lab = np.empty((M, Hl, Wl), np.uint8) if with_labels else None
+        dep = np.empty((M, Hs, Ws), np.uint8) if use_depth else None
+
+        def put(dst, k, a, path, kind):
+            if a.shape != dst.shape[1:]:
+                raise RuntimeError('mspl_amd: FrameStore: %s %s is %dx%d, the first one (%s) is %dx%d'
+                                   % (kind, path, a.shape[1], a.shape[0], {'frame': images, 'label': masks, 'depth': depths}[kind][0],
+                                      dst.shape[2], dst.shape[1]))
+            dst[k] = a
+
+        def decode(k):
+            with Image.open(images[k]) as im:
+                put(rgb, k, np.asarray(im.convert('RGB')), images[k], 'frame')
+            if with_labels:
+                with Image.open(masks[k]) as im:
+                    a = np.array(im, np.uint8)
+                if a.ndim != 2:
+                    raise RuntimeError('mspl_amd: FrameStore: label %s is not a single-channel image (array shape %s)' % (masks[k], a.shape))
+                put(lab, k, a, masks[k], 'label')
+            if use_depth:
+                put(dep, k, _decode_depth_u8(depths[k]), depths[k], 'depth')
+        limit = min(16, host_cores())
+        workers = limit if workers is None else max(1, min(int(workers), limit))
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            list(pool.map(decode, range(M)))                        # the first error of a file, in list order, is raised here
+        return cls.from_arrays(rgb, lab, dep, names=images, device=device)
+
+    def put_labels(self, names, maps_u8, stream=None):
+        """The `label_sink` of generate_pseudo_label*: the (n,Hl,Wl) uint8 device maps of `names` go into their slots by one
+        device-to-device copy, issued on `stream` (or the current stream).  `labels` is allocated at the first call."""
+        names = list(names)
+        if (not isinstance(maps_u8, torch.Tensor) or maps_u8.dtype != torch.uint8 or maps_u8.dim() != 3 or maps_u8.shape[0] != len(names)
+                or maps_u8.device != self.device):
+            raise RuntimeError('mspl_amd: FrameStore.put_labels expects (n,Hl,Wl) uint8 maps on %s and n names, got %s %s / %d names'
+                               % (self.device, getattr(maps_u8, 'dtype', type(maps_u8)), tuple(getattr(maps_u8, 'shape', ())), len(names)))
+        dst, src = [], []
+        for k, n in enumerate(names):
+            if n not in self._slots:
+                raise KeyError('mspl_amd: FrameStore.put_labels: %r is not a frame of this store' % (n,))
+            for s in self._slots[n]:
+                dst.append(s)
+                src.append(k)
+        if self.labels is None:
+            # uninitialised on purpose: a fill on the current stream could land after a copy on `stream`; `labelled` says what is valid
+            self.labels = torch.empty((len(self),) + tuple(maps_u8.shape[1:]), dtype=torch.uint8, device=self.device)
+        elif tuple(maps_u8.shape[1:]) != tuple(self.labels.shape[1:]):
+            raise RuntimeError('mspl_amd: FrameStore.put_labels: maps of %dx%d, the store holds %dx%d'
+                               % (maps_u8.shape[2], maps_u8.shape[1], self.labels.shape[2], self.labels.shape[1]))
+        if not dst:
+            return
+        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+        with ctx:
+            if src == list(range(len(names))) and dst == list(range(dst[0], dst[0] + len(dst))):
+                self.labels[dst[0]:dst[0] + len(dst)].copy_(maps_u8, non_blocking=True)           # consecutive slots: one plain copy
+            else:
+                idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
+                rows = maps_u8 if src == list(range(len(names))) else maps_u8[torch.tensor(src).to(self.device)]
+                self.labels.index_copy_(0, idx, rows)
+        self.labelled[dst] = True
+
+    def frames(self, batch_size):
+        """Iterable over consecutive slots yielding `(rgb_u8_view, None, names, None)` -- `(rgb_u8_view, None, depth_view, names,
+        None)` with depth --: views, not copies, in the tuple shape the label loop reads (batch[0], batch[-2])."""
+        return _StoreFrames(self, batch_size)
+
+
+class ResidentTrainLoader(object):
+    """The train loader of the self-training rounds over a FrameStore: yields the reference dataset's batch after default collation
+    (greenhouse.py:267-270) with the tensors on the device --
+
+        (images fp32 (n,3,H,W), labels int64 (n,H,W), names list, reg float64 (n,))            or, with use_depth,
+        (images, labels, depth fp32 (n,1,H,W), names, reg)
+
+    -- from one TrainPreprocessor call per batch that reads the store by slot.  The batch order is a real torch DataLoader's over
+    the slot numbers (`shuffle`, `drop_last`, `sampler` are its arguments; a DistributedSampler gives each rank its shard), so the
+    order and the torch RNG consumption are torch's own; the augmentation draws are `preprocessor.draw(n, (Ws, Hs))` once per batch:
+    the reference's per-image draws in sampler order from the module-level `random`.  Everything runs on the current stream and
+    nothing synchronises.  label_lut: 256 uint8 values, the dataset's label remap (greenhouse.py:248-251: lut[0] = 1)."""
+
+    def __init__(self, store, preprocessor, batch_size, shuffle=True, drop_last=False, sampler=None, use_depth=False, reg_weight=0.0,
+                 label_lut=None):
+        from torch.utils.data import DataLoader
+        if use_depth and store.depth is None:
+            raise RuntimeError('mspl_amd: ResidentTrainLoader: use_depth with a store that holds no depth maps')
+        self.store, self.preprocessor, self.use_depth, self.reg_weight = store, preprocessor, bool(use_depth), float(reg_weight)
+        self.label_lut = None
+        if label_lut is not None:
+            lut = torch.as_tensor(label_lut)
+            if lut.dtype != torch.uint8 or lut.numel() != 256:
+                raise RuntimeError('mspl_amd: label_lut must hold 256 uint8 values, got %s %s' % (lut.dtype, tuple(lut.shape)))
+            self.label_lut = lut.to(store.device).contiguous()
+        self._index = DataLoader(range(len(store)), batch_size=batch_size, shuffle=bool(shuffle) and sampler is None, sampler=sampler,
+                                 drop_last=drop_last, num_workers=0, collate_fn=list)
+        self.batch_size, self.sampler = batch_size, self._index.sampler
+
+    def __len__(self):
+        return len(self._index)
+
+    def __iter__(self):
+        s, pre = self.store, self.preprocessor
+        if s.labels is None:
+            raise RuntimeError('mspl_amd: ResidentTrainLoader: the store has no labels yet (FrameStore.put_labels)')
+        Hs, Ws = s.rgb.shape[1:3]
+        for slots in self._index:
+            slots = [int(k) for k in slots]
+            if not s.labelled[slots].all():
+                raise RuntimeError('mspl_amd: ResidentTrainLoader: slot %d has no label map yet'
+                                   % [k for k in slots if not s.labelled[k]][0])
+            x, y, d = pre(s.rgb, s.labels, s.depth if self.use_depth else None, params=pre.draw(len(slots), (Ws, Hs)), slots=slots,
+                          label_lut=self.label_lut)
+            names = [s.names[k] for k in slots]
+            reg = torch.full((len(slots),), self.reg_weight, dtype=torch.float64, device=s.device)
+            yield (x, y, d, names, reg) if self.use_depth else (x, y, names, reg)
 
 
 # ------------------------------------------------------------------ label PNG writer

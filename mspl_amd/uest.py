@@ -498,15 +498,21 @@ class PipelinedLabelPass:
 
 
 def _label_loop(p, testloader, save_path, labels_of, class_weighting, use_depth, device, writer_workers, pre_sharded, transform,
-                eager_input):
+                eager_input, label_sink=None):
     """Loop + files + list + class weights shared by the two label functions (uest_seg_multi_os.py:783-828 and :889-954 are the same
     code around different loop bodies).  `p`: PipelinedLabelPass interface; labels_of(result) -> the (N,H,W) uint8 maps of one batch.
     transform(image, out=slot) -> network input: the loader may then yield decoded uint8 frames (N,Hs,Ws,3), host or device, and the
-    transform (mspl_amd.io.Preprocessor) writes the network input straight into the static input slot of the lane that labels it."""
+    transform (mspl_amd.io.Preprocessor) writes the network input straight into the static input slot of the lane that labels it.
+    label_sink(names, maps_u8_device, stream): also receives every batch's maps on the device (mspl_amd.io.FrameStore.put_labels), on
+    the stream of the lane that produced them (None: the current stream) and BEFORE the writer's submit for that batch -- the writer's
+    copy follows the sink's on that stream, so when writer.close() has returned the sink's copies have run."""
     import os.path as osp
     from . import dist as mdist
     from .io import LabelWriter, default_writer_workers, update_image_list
     rank, world = mdist.world()
+    if label_sink is not None and world > 1:
+        raise RuntimeError('mspl_amd: label_sink with %d ranks: the ranks label disjoint batches and a resident store needs the maps '
+                           'of all of them; multi-GPU runs stay on the list-file path' % world)
     p.reset()
     tgt_train_lst = osp.join(save_path, 'tgt_train.lst')
     if writer_workers is None:
@@ -520,10 +526,14 @@ def _label_loop(p, testloader, save_path, labels_of, class_weighting, use_depth,
     on_lane = isinstance(p, PipelinedLabelPass)
 
     def consume(r):
+        batch_names = names.pop(0)
+        maps, stream = (labels_of(r[0]), r[1]) if on_lane else (labels_of(r), None)
+        if label_sink is not None:
+            label_sink(batch_names, maps, stream)
         if on_lane:
-            writer.submit(names.pop(0), labels_of(r[0]), stream=r[1])
+            writer.submit(batch_names, maps, stream=stream)
         else:
-            writer.submit(names.pop(0), labels_of(r))
+            writer.submit(batch_names, maps)
     for b, batch in enumerate(testloader):
         if world > 1 and not pre_sharded and b % world != rank:
             continue
@@ -573,7 +583,7 @@ def _label_loop(p, testloader, save_path, labels_of, class_weighting, use_depth,
 def generate_pseudo_label_multi_model(model_list, os_data_list, testloader, save_path, classes=GREENHOUSE_CLASSES,
                                       merge_label_policy='all', class_weighting='normal', use_depth=False, device='cuda',
                                       use_graph=True, writer_workers=None, in_flight=3, pre_sharded=False, _label_pass=None,
-                                      batches_per_launch=1, transform=None, eval_training=False):
+                                      batches_per_launch=1, transform=None, eval_training=False, label_sink=None):
     """uest_seg_multi_os.py:832-956 end to end: label every batch of `testloader` with all source models, merge, write
     `<save_path>/pred/<image_name>.png`, write `<save_path>/tgt_train.lst` and return (tgt_train_lst, class_weights).
 
@@ -589,19 +599,19 @@ def generate_pseudo_label_multi_model(model_list, os_data_list, testloader, save
     weights.  pre_sharded=True: the caller's loader already yields this rank's batches only (e.g. a sampler over
     dist.shard_indices) -- use it when skipping a foreign batch is not free (the loader decodes it first).
     `_label_pass`: an object with PipelinedLabelPass's interface, for host-logic tests.  batches_per_launch: PipelinedLabelPass's
-    `group` (consecutive loader batches labelled by one launch; worth ~5 % at batch 16).  transform: see _label_loop."""
+    `group` (consecutive loader batches labelled by one launch; worth ~5 % at batch 16).  transform, label_sink: see _label_loop."""
     p = _label_pass if _label_pass is not None else PipelinedLabelPass(
         lambda: PseudoLabelPass(model_list, os_data_list, classes=classes, merge_label_policy=merge_label_policy,
                                 device=device, use_graph=use_graph, eval_training=eval_training),
         # eval_training: the images update the models' running statistics in loader order -- one lane, one batch per launch
         depth=1 if eval_training else in_flight, device=device, group=1 if eval_training else batches_per_launch)
     return _label_loop(p, testloader, save_path, lambda out: out, class_weighting, use_depth, device, writer_workers, pre_sharded,
-                       transform, _label_pass is not None)
+                       transform, _label_pass is not None, label_sink)
 
 
 def generate_pseudo_label(model, testloader, save_path, classes=GREENHOUSE_CLASSES, class_weighting='normal', use_depth=False,
                           device='cuda', use_graph=True, writer_workers=None, in_flight=3, batches_per_launch=2, pre_sharded=False,
-                          _label_pass=None, transform=None, eval_training=False):
+                          _label_pass=None, transform=None, eval_training=False, label_sink=None):
     """uest_seg_multi_os.py:730-830 end to end, the single-model relabelling of every self-training round (called at :527-528):
     loader -> get_output (`softmax(pred + 0.5 aux)`, :795) -> argmax (:798) -> `class_array` (:800-801) -> `<save_path>/pred/<image_name>.png`
     (:803-811) -> path lists (:813-816) -> update_image_list (:820) -> class weights (:822-828); returns (tgt_train_lst, class_weights).
@@ -609,7 +619,7 @@ def generate_pseudo_label(model, testloader, save_path, classes=GREENHOUSE_CLASS
     The loop body is SelfLabelPass (forward + fused epilogue: up-sampling of both heads, argmax of pred + 0.5 aux -- softmax is
     monotone, the probabilities are never written -- and the class histogram), `in_flight` launches of `batches_per_launch` loader
     batches each overlap on the GPU, the PNG files are written by LabelWriter's native threads.  Loader tuples, rank sharding,
-    `pre_sharded`, `_label_pass` and `transform` as in generate_pseudo_label_multi_model.  The reference's loader is batch size 1
+    `pre_sharded`, `_label_pass`, `transform` and `label_sink` as in generate_pseudo_label_multi_model.  The reference's loader is batch size 1
     (:746); BatchNorm is in eval mode, so any batch size gives the same maps.  eval_training=True is the reference's
     `--eval-training` (:749-752): train() mode under no_grad, i.e. BatchNorm with the statistics of each single image (and the
     momentum updates of the running statistics that come with it) -- `_lowres_batch_stats`; one lane, no graph."""
@@ -617,7 +627,7 @@ def generate_pseudo_label(model, testloader, save_path, classes=GREENHOUSE_CLASS
         lambda: SelfLabelPass(model, classes=classes, device=device, use_graph=use_graph, with_kld=False, eval_training=eval_training),
         depth=1 if eval_training else in_flight, device=device, group=1 if eval_training else batches_per_launch)
     return _label_loop(p, testloader, save_path, lambda out: out[0] if isinstance(out, (tuple, list)) else out, class_weighting,
-                       use_depth, device, writer_workers, pre_sharded, transform, _label_pass is not None)
+                       use_depth, device, writer_workers, pre_sharded, transform, _label_pass is not None, label_sink)
 
 
 class SelfLabelPass(_GraphedPassMixin):
