@@ -392,6 +392,35 @@ int mspl_label_epilogue_fwd(const float* main, const float* aux, int32_t N, int3
                             const uint8_t* lut, uint8_t* labels, float* prob, float* kld,
                             float* main_up, float* aux_up, void* stream);
 
+/* The kernel form mspl_label_epilogue_fwd / _hist_fwd / _planes_fwd take for these shapes (espdnet_ue.py:301-302 +
+ *     uest_seg_multi_os.py:685-691, :903-912: the arithmetic is the same in every form, labels and KL map of the two label forms
+ *     bit for bit).  Host only, no device call, no state: it returns what the host function the launcher itself switches on
+ *     returns, and mspl_label_epilogue_hist_fits asks the same function.
+ *     Ha = Wa = 0: no second head.  general: prob, main_up or aux_up is requested.  aligned16: both heads' base pointers are
+ *     16-byte aligned.  out: MSPL_LE_PLAN_LEN entries; what does not apply to the form is 0.  (The tuning variable MSPL_LE_REG,
+ *     which forces the register form, is not seen here.) */
+#define MSPL_LE_FORM_GENERAL 0          /* one thread per pixel, any C, every output */
+#define MSPL_LE_FORM_REGISTER 1         /* labels / KL map, C <= 24, logits read from memory per pixel */
+#define MSPL_LE_FORM_LDS 2              /* labels / KL map (/ histogram / planes), source rows of a 4 x 256 tile staged in LDS */
+#define MSPL_LE_PLAN_FORM 0             /* MSPL_LE_FORM_* */
+#define MSPL_LE_PLAN_VEC 1              /* LDS: 1 = 16-byte staging chunks, 0 = 4-byte */
+#define MSPL_LE_PLAN_NRM 2              /* LDS: staged source rows per band, main / aux head */
+#define MSPL_LE_PLAN_NRA 3
+#define MSPL_LE_PLAN_WMS 4              /* LDS: staged columns per row (the row stride), main / aux head */
+#define MSPL_LE_PLAN_WAS 5
+#define MSPL_LE_PLAN_LDS_BYTES 6        /* LDS: dynamic LDS of the launch */
+#define MSPL_LE_PLAN_PAIRS_MAIN 7       /* LDS: largest number of staged (row, class) pairs of a tile, per head; the decode of a */
+#define MSPL_LE_PLAN_PAIRS_AUX 8        /*      pair index is exact below 4096 and the form requires their sum to stay below it */
+#define MSPL_LE_PLAN_CMAX 9             /* register / LDS: class count the kernel is instantiated for (8, 16, 24; LDS also 5, 13, 20) */
+#define MSPL_LE_PLAN_EXACT 10           /* LDS: 1 = C == CMAX, no per-class predicates */
+#define MSPL_LE_PLAN_WIDE480 11         /* LDS: 1 = the compile-time row strides 132 / 68 */
+#define MSPL_LE_PLAN_BANDS 12           /* LDS: bands of 4 output rows; register: output rows */
+#define MSPL_LE_PLAN_COLBLOCKS 13       /* register / LDS: blocks of 256 output columns (grid x) */
+#define MSPL_LE_PLAN_ROWSLOTS 14        /* register / LDS: grid y, bands / rows padded to a multiple of 4 (XCD order) */
+#define MSPL_LE_PLAN_LEN 15
+int mspl_label_epilogue_plan(int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
+                             int32_t general, int32_t aligned16, int32_t* out);
+
 /* K8+K9 with the class histogram of the labels it writes: the single-source label pass (uest_seg_multi_os.py:785-815,
  *     one model relabelling its own domain) without a separate merge launch -- what label_epilogue + merge_labels(S=1,
  *     thresh=1) computed.  hist: num_classes (<= 32) uint64 bins, accumulated into (caller zeroes); labels >= num_classes
@@ -400,7 +429,8 @@ int mspl_label_epilogue_fwd(const float* main, const float* aux, int32_t N, int3
  *     same-address device atomics from ~10^4 workgroups serialise).
  */
 int64_t mspl_label_epilogue_hist_workspace_bytes(int32_t N, int32_t H, int32_t W);
-/* 1 when mspl_label_epilogue_hist_fwd covers the shape (the LDS-staged tile of both heads fits; Ha = Wa = 0: no second head);
+/* 1 when mspl_label_epilogue_hist_fwd covers the shape (the LDS-staged tile of both heads fits; Ha = Wa = 0: no second head),
+ * whatever the alignment of the pointers: mspl_label_epilogue_plan answers MSPL_LE_FORM_LDS with aligned16 = 1 and with 0;
  * callers run mspl_label_epilogue_fwd + mspl_merge_labels_fwd(S = 1, thresh = 1) otherwise. */
 int mspl_label_epilogue_hist_fits(int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W);
 int mspl_label_epilogue_hist_fwd(const float* main, const float* aux, int32_t N, int32_t C,

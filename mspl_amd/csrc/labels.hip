@@ -757,6 +757,53 @@ using namespace mspl;
 
 static int64_t le_blocks(int N, int H, int W) { return (int64_t)ceil_div(W, 256) * (4 * ceil_div(ceil_div(H, LE_RB), 4)) * N; }
 
+// The one place the form of a label-epilogue launch is decided: label_epilogue_impl launches what this returns,
+// mspl_label_epilogue_hist_fits and mspl_label_epilogue_plan report it.  Shapes and two facts about the call only.
+//   general:   probabilities or up-sampled logits are asked for (label_epilogue_kernel writes them; the label forms do not)
+//   aligned16: both heads' base pointers are 16-byte aligned (16-byte staging chunks need that and rows of a multiple of 4)
+//   no_lds:    the tuning aid MSPL_LE_REG (label_epilogue_impl alone passes it): the register form where the LDS form would fit
+// Ha = Wa = 0: no second head.
+struct LePlan {
+    int form;                       // MSPL_LE_FORM_*
+    int vec, nrm, nra, wms, was;    // LeStage's
+    size_t lds;                     // bytes of dynamic LDS
+    int cmax, exact, wide480;       // instantiation: label_epilogue_lds_kernel<cmax, exact, wide480 ? 132 : 0, wide480 ? 68 : 0> / reg_kernel<cmax>
+    int bands, colblocks, rowslots; // LDS form: bands of LE_RB rows; register form: rows.  Grid = (colblocks, rowslots, N)
+};
+
+static LePlan le_plan(int N, int C, int Hm, int Wm, int Ha, int Wa, int H, int W, bool general, bool aligned16, bool no_lds = false) {
+    LePlan p;
+    memset(&p, 0, sizeof(p));
+    p.form = MSPL_LE_FORM_GENERAL;
+    const bool aux = Ha > 0 && Wa > 0;
+    const bool label_form = !general && C <= 24 && H <= 65535 * LE_RB / 4 && N <= 65535 &&
+                            (int64_t)N * C * Hm * Wm < (1ll << 31) && (int64_t)N * C * (int64_t)Ha * Wa < (1ll << 31);
+    if (!label_form) return p;
+    // LDS-staged form when the tile's source rows fit (they do for the x2 / x4 heads of the path); else the register form
+    p.vec = (Wm % 4 == 0) && (!aux || Wa % 4 == 0) && aligned16;
+    p.nrm = bilinear_span(Hm, H, LE_RB, false);  p.wms = bilinear_span(Wm, W, 256, p.vec);
+    p.nra = aux ? bilinear_span(Ha, H, LE_RB, false) : 0;  p.was = aux ? bilinear_span(Wa, W, 256, p.vec) : 4;
+    if (!p.vec) { p.wms = (p.wms + 3) & ~3; p.was = (p.was + 3) & ~3; }      // keep the second head's base 16-byte aligned
+    p.lds = ((size_t)p.nrm * C * p.wms + (size_t)p.nra * C * p.was + 32) * sizeof(float);
+    p.cmax = C <= 8 ? 8 : C <= 16 ? 16 : 24;
+    p.colblocks = ceil_div(W, 256);
+    // (nrm + nra) * C < 4096: the staged pair index stays inside the range the magic division by C is exact on (LeStage::magc:
+    // pair * (magc * C - 65536) < 65536 holds for every C <= 24 and pair < 4096; C = 17 is the tightest, 4095 * 16 = 65520)
+    if (!no_lds && p.lds <= 128 * 1024 && (p.nrm + p.nra) * C < 4096 && p.wms <= 256 && p.was <= 256) {
+        p.form = MSPL_LE_FORM_LDS;
+        p.exact = C == 5 || C == 13 || C == 20;
+        if (p.exact) p.cmax = C;
+        p.wide480 = p.exact && p.wms == 132 && (!aux || p.was == 68);     // the x2 / x4 heads of 480-pixel-wide images
+        p.bands = ceil_div(H, LE_RB);
+        p.rowslots = 4 * ceil_div(p.bands, 4);
+    } else {
+        p.form = MSPL_LE_FORM_REGISTER;
+        p.bands = H;
+        p.rowslots = 4 * ceil_div(H, 4);                                   // row slots: see the kernel
+    }
+    return p;
+}
+
 static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, int32_t C,
                                int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
                                const uint8_t* lut, uint8_t* labels, float* prob, float* kld,
@@ -776,32 +823,24 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
     const int64_t total = (int64_t)N * H * W;
     MSPL_REQUIRE(ceil_div64(total, 256) < (1ll << 31), MSPL_ERR_BAD_SHAPE, "label_epilogue: grid too large");
     hipStream_t st_ = (hipStream_t)stream;
-    const bool label_form = !prob && !main_up && !aux_up && C <= 24 && H <= 65535 * LE_RB / 4 && N <= 65535 &&
-                            (int64_t)N * C * Hm * Wm < (1ll << 31) && (int64_t)N * C * (int64_t)Ha * Wa < (1ll << 31);
+    static const int dbg_reg = MSPL_TUNE_INT("MSPL_LE_REG", 0);     // tuning aid: force the register form (not seen by the plan query)
+    const LePlan pl = le_plan(N, C, Hm, Wm, aux ? Ha : 0, aux ? Wa : 0, H, W, prob || main_up || aux_up,
+                              (((uintptr_t)mainp) & 15) == 0 && (((uintptr_t)aux) & 15) == 0, dbg_reg && !hist && !planes);
     LePlanes lp;
     memset(&lp, 0, sizeof(lp));
     if (planes) lp = *planes;
-    if (label_form) {
-        // LDS-staged form when the tile's source rows fit (they do for the x2 / x4 heads of the path); else the register form
+    if (pl.form != MSPL_LE_FORM_GENERAL) {
         LeStage st;
-        st.vec = (Wm % 4 == 0) && (!aux || Wa % 4 == 0) && (((uintptr_t)mainp) & 15) == 0 && (((uintptr_t)aux) & 15) == 0;
-        st.nrm = bilinear_span(Hm, H, LE_RB, false);  st.wms = bilinear_span(Wm, W, 256, st.vec);
-        st.nra = aux ? bilinear_span(Ha, H, LE_RB, false) : 0;  st.was = aux ? bilinear_span(Wa, W, 256, st.vec) : 4;
-        if (!st.vec) { st.wms = (st.wms + 3) & ~3; st.was = (st.was + 3) & ~3; }      // keep the second head's base 16-byte aligned
+        st.vec = pl.vec;  st.nrm = pl.nrm;  st.nra = pl.nra;  st.wms = pl.wms;  st.was = pl.was;
         st.ncls = hist ? ncls : 0;
         st.magc = (65536u + (unsigned)C - 1) / (unsigned)C;
+        // lane / (chunks per pair) for lane < 64: with cq = wms / 4 (was / 4) <= 64 in the LDS form, mag = ceil(2^20 / cq) has
+        // mag * cq - 2^20 < cq <= 64, so lane * (mag * cq - 2^20) < 64 * 64 < 2^20 and (lane * mag) >> 20 == lane / cq exactly
         st.magqm = ((1u << 20) + (unsigned)(st.wms >> 2) - 1) / (unsigned)(st.wms >> 2);
         st.magqa = ((1u << 20) + (unsigned)(st.was >> 2) - 1) / (unsigned)(st.was >> 2);
-        {   // exactness of the two magic divisions over the ranges used (else: 4-byte staging, which needs neither)
-            bool ok = true;                                        // lane / (chunks per pair) for lane < 64
-            for (int k = 0; k < 64 && ok; ++k) ok = (int)(((unsigned)k * st.magqm) >> 20) == k / (st.wms >> 2);
-            for (int k = 0; k < 64 && ok; ++k) ok = (int)(((unsigned)k * st.magqa) >> 20) == k / (st.was >> 2);
-            if (!ok) st.vec = 0;
-        }
-        const size_t lds = ((size_t)st.nrm * C * st.wms + (size_t)st.nra * C * st.was + 32) * sizeof(float);
-        static const int dbg_reg = MSPL_TUNE_INT("MSPL_LE_REG", 0);     // tuning aid: force the register form
-        if (lds <= 128 * 1024 && (st.nrm + st.nra) * C < 4096 && st.wms <= 256 && st.was <= 256 && (!st.vec || (st.wms <= 256 && st.was <= 256)) && !(dbg_reg && !hist && !planes)) {
-            const dim3 grid((unsigned)ceil_div(W, 256), (unsigned)(4 * ceil_div(ceil_div(H, LE_RB), 4)), (unsigned)N);
+        const size_t lds = pl.lds;
+        if (pl.form == MSPL_LE_FORM_LDS) {
+            const dim3 grid((unsigned)pl.colblocks, (unsigned)pl.rowslots, (unsigned)N);
             unsigned int* ws = nullptr;
             if (hist) {
                 const int64_t need = le_blocks(N, H, W) * 32 * (int64_t)sizeof(unsigned int);
@@ -826,11 +865,11 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
 #define MSPL_LE_KERNEL(CM, EX, A, B) do { if (planes) hipLaunchKernelGGL((label_epilogue_lds_kernel<CM, EX, A, B, true>), grid, dim3(256), lds, st_, mainp, aux, g, st, lp, lut, labels, kld, ws); \
                                          else hipLaunchKernelGGL((label_epilogue_lds_kernel<CM, EX, A, B, false>), grid, dim3(256), lds, st_, mainp, aux, g, st, lp, lut, labels, kld, ws); } while (0)
 #define MSPL_LE_LAUNCH(CM, EX) do { if (wide480) MSPL_LE_KERNEL(CM, EX, 132, 68); else MSPL_LE_KERNEL(CM, EX, 0, 0); } while (0)
-            const bool wide480 = (C == 5 || C == 13 || C == 20) && st.wms == 132 && (!aux || st.was == 68);     // the x2 / x4 heads of 480-pixel-wide images
+            const bool wide480 = pl.wide480;                     // only ever set with C = 5 / 13 / 20 (le_plan)
             if (C == 5) MSPL_LE_LAUNCH(5, true);
             else if (C == 13) MSPL_LE_LAUNCH(13, true);
             else if (C == 20) MSPL_LE_LAUNCH(20, true);
-            else if (C <= 8) { if (wide480) return MSPL_ERR_UNSUPPORTED; MSPL_LE_KERNEL(8, false, 0, 0); }
+            else if (C <= 8) MSPL_LE_KERNEL(8, false, 0, 0);
             else if (C <= 16) MSPL_LE_KERNEL(16, false, 0, 0);
             else MSPL_LE_KERNEL(24, false, 0, 0);
 #undef MSPL_LE_LAUNCH
@@ -844,10 +883,10 @@ static int label_epilogue_impl(const float* mainp, const float* aux, int32_t N, 
         }
         MSPL_REQUIRE(!hist && !planes, MSPL_ERR_UNSUPPORTED, "label_epilogue_hist: tile does not fit the LDS-staged form (N=%d C=%d %dx%d -> %dx%d)",
                      N, C, Hm, Wm, H, W);
-        const dim3 grid((unsigned)ceil_div(W, 256), (unsigned)(4 * ceil_div(H, 4)), (unsigned)N);     // row slots: see the kernel
+        const dim3 grid((unsigned)pl.colblocks, (unsigned)pl.rowslots, (unsigned)N);     // row slots: see the kernel
         MSPL_REQUIRE(H <= 65535, MSPL_ERR_BAD_SHAPE, "label_epilogue: %d rows", H);
-        if (C <= 8) hipLaunchKernelGGL(label_epilogue_reg_kernel<8>, grid, dim3(256), 0, st_, mainp, aux, g, lut, labels, kld);
-        else if (C <= 16) hipLaunchKernelGGL(label_epilogue_reg_kernel<16>, grid, dim3(256), 0, st_, mainp, aux, g, lut, labels, kld);
+        if (pl.cmax == 8) hipLaunchKernelGGL(label_epilogue_reg_kernel<8>, grid, dim3(256), 0, st_, mainp, aux, g, lut, labels, kld);
+        else if (pl.cmax == 16) hipLaunchKernelGGL(label_epilogue_reg_kernel<16>, grid, dim3(256), 0, st_, mainp, aux, g, lut, labels, kld);
         else hipLaunchKernelGGL(label_epilogue_reg_kernel<24>, grid, dim3(256), 0, st_, mainp, aux, g, lut, labels, kld);
         MSPL_CHECK_LAUNCH("label_epilogue");
         return MSPL_OK;
@@ -873,18 +912,32 @@ extern "C" int64_t mspl_label_epilogue_hist_workspace_bytes(int32_t N, int32_t H
 }
 
 extern "C" int mspl_label_epilogue_hist_fits(int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W) {
-    // the conditions of the LDS-staged label form in label_epilogue_impl (the only form that accumulates the histogram)
-    if (N <= 0 || C <= 0 || C > 24 || Hm <= 0 || Wm <= 0 || H <= 0 || W <= 0 || Ha < 0 || Wa < 0) return 0;
-    const bool aux = Ha > 0 && Wa > 0;
-    if (!(H <= 65535 * LE_RB / 4 && N <= 65535 && (int64_t)N * C * Hm * Wm < (1ll << 31) && (int64_t)N * C * (int64_t)Ha * Wa < (1ll << 31))) return 0;
-    const bool vec = (Wm % 4 == 0) && (!aux || Wa % 4 == 0);      // (pointer alignment can only shrink the tile: unaligned = 4-byte staging)
-    const int nrm = bilinear_span(Hm, H, LE_RB, false), nra = aux ? bilinear_span(Ha, H, LE_RB, false) : 0;
-    int wms = bilinear_span(Wm, W, 256, vec), was = aux ? bilinear_span(Wa, W, 256, vec) : 4;
-    if (!vec) { wms = (wms + 3) & ~3; was = (was + 3) & ~3; }
-    const int wms4 = (bilinear_span(Wm, W, 256, true) + 3) & ~3, was4 = aux ? (bilinear_span(Wa, W, 256, true) + 3) & ~3 : 4;   // worst case of either staging
-    wms = std::max(wms, wms4); was = std::max(was, was4);
-    const size_t lds = ((size_t)nrm * C * wms + (size_t)nra * C * was + 32) * sizeof(float);
-    return lds <= 128 * 1024 && (nrm + nra) * C < 4096 && wms <= 256 && was <= 256;
+    // the LDS-staged label form (the only one that accumulates the histogram), whatever the alignment of the pointers (16-byte
+    // staging has the larger tile -- first column rounded down, count rounded up -- so it decides; both are asked all the same)
+    if (N <= 0 || C <= 0 || Hm <= 0 || Wm <= 0 || H <= 0 || W <= 0 || Ha < 0 || Wa < 0) return 0;
+    return le_plan(N, C, Hm, Wm, Ha, Wa, H, W, false, true).form == MSPL_LE_FORM_LDS &&
+           le_plan(N, C, Hm, Wm, Ha, Wa, H, W, false, false).form == MSPL_LE_FORM_LDS;
+}
+
+extern "C" int mspl_label_epilogue_plan(int32_t N, int32_t C, int32_t Hm, int32_t Wm, int32_t Ha, int32_t Wa, int32_t H, int32_t W,
+                                        int32_t general, int32_t aligned16, int32_t* out) {
+    MSPL_REQUIRE(out, MSPL_ERR_NULL_POINTER, "label_epilogue_plan: null out");
+    MSPL_REQUIRE(N > 0 && C > 0 && Hm > 0 && Wm > 0 && H > 0 && W > 0 && Ha >= 0 && Wa >= 0 && (Ha > 0) == (Wa > 0), MSPL_ERR_BAD_SHAPE,
+                 "label_epilogue_plan: bad shape N=%d C=%d main=%dx%d aux=%dx%d out=%dx%d", N, C, Hm, Wm, Ha, Wa, H, W);
+    MSPL_REQUIRE(C <= 255, MSPL_ERR_UNSUPPORTED, "label_epilogue_plan: %d classes do not fit a uint8 label", C);
+    const LePlan p = le_plan(N, C, Hm, Wm, Ha, Wa, H, W, general != 0, aligned16 != 0);
+    for (int i = 0; i < MSPL_LE_PLAN_LEN; ++i) out[i] = 0;
+    out[MSPL_LE_PLAN_FORM] = p.form;
+    if (p.form == MSPL_LE_FORM_GENERAL) return MSPL_OK;
+    out[MSPL_LE_PLAN_CMAX] = p.cmax;
+    out[MSPL_LE_PLAN_BANDS] = p.bands;  out[MSPL_LE_PLAN_COLBLOCKS] = p.colblocks;  out[MSPL_LE_PLAN_ROWSLOTS] = p.rowslots;
+    if (p.form != MSPL_LE_FORM_LDS) return MSPL_OK;
+    out[MSPL_LE_PLAN_VEC] = p.vec;
+    out[MSPL_LE_PLAN_NRM] = p.nrm;  out[MSPL_LE_PLAN_NRA] = p.nra;  out[MSPL_LE_PLAN_WMS] = p.wms;  out[MSPL_LE_PLAN_WAS] = p.was;
+    out[MSPL_LE_PLAN_LDS_BYTES] = (int32_t)p.lds;
+    out[MSPL_LE_PLAN_PAIRS_MAIN] = p.nrm * C;  out[MSPL_LE_PLAN_PAIRS_AUX] = p.nra * C;
+    out[MSPL_LE_PLAN_EXACT] = p.exact;  out[MSPL_LE_PLAN_WIDE480] = p.wide480;
+    return MSPL_OK;
 }
 
 extern "C" int mspl_label_epilogue_hist_fwd(const float* mainp, const float* aux, int32_t N, int32_t C,

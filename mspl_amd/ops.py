@@ -692,6 +692,24 @@ def label_epilogue_hist_fits(main, aux, size):
     return bool(lib.mspl_label_epilogue_hist_fits(N, C, Hm, Wm, Ha, Wa, int(size[0]), int(size[1])))
 
 
+LABEL_EPILOGUE_FORMS = ('general', 'register', 'lds')      # MSPL_LE_FORM_*
+_LE_PLAN_FIELDS = ('VEC', 'NRM', 'NRA', 'WMS', 'WAS', 'LDS_BYTES', 'PAIRS_MAIN', 'PAIRS_AUX', 'CMAX', 'EXACT', 'WIDE480', 'BANDS',
+                   'COLBLOCKS', 'ROWSLOTS')
+
+
+def label_epilogue_plan(shape, general=False, aligned16=True):
+    """The kernel form the label epilogue takes (mspl_label_epilogue_plan, the launcher's own host function; no device call).
+    shape: (N, C, Hm, Wm, Ha, Wa, H, W), Ha = Wa = 0 without a second head; general: probabilities or up-sampled logits are
+    asked for; aligned16: both heads' base pointers are 16-byte aligned.  -> dict form ('general' / 'register' / 'lds') and the
+    integers vec / nrm / nra / wms / was / lds_bytes / pairs_main / pairs_aux / cmax / exact / wide480 / bands / colblocks /
+    rowslots, 0 where they do not apply to the form."""
+    out = (ctypes.c_int32 * nat.LE_PLAN_LEN)()
+    check(lib.mspl_label_epilogue_plan(*[int(v) for v in shape], int(bool(general)), int(bool(aligned16)), out))
+    plan = {n.lower(): int(out[getattr(nat, 'LE_PLAN_' + n)]) for n in _LE_PLAN_FIELDS}
+    plan['form'] = LABEL_EPILOGUE_FORMS[int(out[nat.LE_PLAN_FORM])]
+    return plan
+
+
 def label_epilogue_hist(main, aux, size, hist, num_classes, lut=None, want_kld=False):
     """K8+K9 + class histogram in one launch (single-source pass).  Requires C <= min(24, num_classes) so that every label is a
     counted class -- then it equals label_epilogue followed by merge_labels(S=1, thresh=1).  Returns dict(labels[, kld])."""

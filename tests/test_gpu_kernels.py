@@ -555,9 +555,17 @@ def test_label_epilogue_hist_fits_and_fallback():
     h = torch.zeros(5, dtype=torch.int64, device=DEV)
     with pytest.raises(RuntimeError):
         ops.label_epilogue_hist(main, aux, (64, 300), h, 5)
-    two = ops.label_epilogue(main, aux, (64, 300))
+    two = ops.label_epilogue(main, aux, (64, 300), want_kld=True)
     ops.merge_labels([two['labels']], 5, 1, 4, h)
     assert int(h.sum()) == 2 * 64 * 300
+    # the register form's labels and KL map against float64 (the rule and the bound of tests/label_cases.py)
+    from tests import label_cases as lc
+    ref = lc.reference_of(main.cpu(), aux.cpu(), (64, 300))
+    assert ops.label_epilogue_plan((2, 5, 64, 300, 32, 150, 64, 300))['form'] == 'register' and ref['unclear'] <= lc.UNCLEAR_CAP
+    assert torch.equal(two['labels'].cpu().long()[ref['clear']], ref['labels'][ref['clear']])
+    kl_err = float((two['kld'].cpu().double() - ref['kld']).abs().max())
+    print('register form 64x300: KL error %.3e against float64, bound %.3e' % (kl_err, ref['bound']['kld']))
+    assert kl_err <= ref['bound']['kld']
     for C in (3, 8, 11, 16, 19, 24):          # the <8>, <16>, <24> instantiations, with tiles above and below 64 KB
         m2 = rnd(1, C, 96, 240, seed=23 + C, scale=2.0).to(DEV)
         a2 = rnd(1, C, 48, 120, seed=24 + C, scale=2.0).to(DEV)
