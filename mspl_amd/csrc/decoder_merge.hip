@@ -15,8 +15,11 @@
 // dependent round trip per channel: 128 -> 48 at 16 x 72x120 52.2 -> 49.5 us, 256 -> 64 at 36x60 33.5 -> 28.7).  The wave walks the groups outermost.  Per input channel it reads four
 // rows (two output rows + one halo row either side) as 8-byte loads; halo columns come from the neighbouring lanes (DPP), and where
 // the neighbour column belongs to another wave's column block the two edge lanes fetch it themselves.  Per `dec` channel it gathers
-// the 3 x 3 low-resolution samples its four pixels blend.  The next input channel's rows and the next group's low-resolution samples
-// are requested before the current ones are used.  The projection runs on the vector unit, the weight column Wp[0..P-1][c]
+// the 3 x 3 low-resolution samples its four pixels blend.  The next input channel's rows are requested before the current ones are
+// used, into the other of two named register buffers (nothing is copied at a loop's back edge); the low-resolution samples likewise
+// where a group is one fetch, and at the group's start where it is eight.  All loads go through one buffer descriptor per tensor
+// with loop-invariant lane offsets and the channel / plane offset as the scalar operand (no vector address arithmetic per load).
+// The projection runs on the vector unit, the weight column Wp[0..P-1][c]
 // broadcast from LDS (staged once per workgroup), channels ascending: the order of conv1x1_thin_kernel.
 //
 // Operation order per `dec` channel is that of the kernels this launch replaces (common.hpp epi_apply; bilinear_src; the 3x3 tap
@@ -46,13 +49,18 @@ __device__ __forceinline__ float dm_from_right(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true));
 }
 
+typedef unsigned dm_u32x2 __attribute__((ext_vector_type(2)));
+
 constexpr int DM_PS = 16;        // LDS stride of one channel's projection weight column (floats)
 
 // CG / COB: input / output channels per group.  KYOUT: the 3x3 sums run kernel row, input channel, kernel column (the order of
 // gconv3x3_stream_kernel); otherwise input channel, kernel row, kernel column (conv3x3_kernel, dwconv3x3_stream_kernel).
 // SPLIT: waves that share one pixel tile, each walking 1 / SPLIT of the groups; their partial projections are summed through LDS in
 // wave order (small maps: one wave per tile leaves most SIMDs without a wave and the rest with nothing to hide a load behind).
-template <int CG, int COB, int P, bool KYOUT, int SPLIT>
+// EDGE: rows are cut into column blocks (g.ncb > 1), so the halo column of a block's first / last lane is loaded, not shuffled.  A
+// compile-time choice keeps every step of the walk below one straight-line block: with a branch around the edge loads the compiler
+// copied the double buffers at the back edges again and needed 40 more registers.
+template <int CG, int COB, int P, bool KYOUT, int SPLIT, bool EDGE>
 __global__ __launch_bounds__(256) void decoder_merge_kernel(DmParams a, DmGeom g, float* __restrict__ out) {
     constexpr int CH = KYOUT ? CG : 1;          // input channels fetched (and prefetched) together
     constexpr int NCH = CG / CH;
@@ -79,13 +87,19 @@ __global__ __launch_bounds__(256) void decoder_merge_kernel(DmParams a, DmGeom g
     const int y0 = min(rp_raw, (H >> 1) - 1) * 2;                   // dead lanes work on clamped, in-bounds coordinates
     const int col = min(col_raw, W - 2);
     const bool lok = cl > 0, rok = cl < g.LPR - 1 && col_raw + 2 < W;        // neighbour lane holds the neighbour column
-    const bool ledge = g.ncb > 1 && live && cl == 0 && col > 0;               // neighbour column lies in another column block
-    const bool redge = g.ncb > 1 && live && cl == g.LPR - 1 && col + 2 < W;
+    const bool ledge = EDGE && live && cl == 0 && col > 0;                    // neighbour column lies in another column block
+    const bool redge = EDGE && live && cl == g.LPR - 1 && col + 2 < W;
     const bool top_in = y0 > 0, bot_in = y0 + 2 < H;
-    int roff[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) roff[r] = min(max(y0 - 1 + r, 0), H - 1) * W + col;
+    // lane byte offsets into the wave's image, fixed for the whole walk; the channel / plane offset is wave-uniform and travels as
+    // the scalar offset of every load (no per-load vector address arithmetic).  EDGE: every lane issues the edge load; a lane that
+    // has no edge column asks for the wave's first row element again (in range, a line the row load already brings) and drops it.
+    int roff[4], eoff[EDGE ? 4 : 1];
     const int ecol = ledge ? -1 : 2;                                // edge column relative to col
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        roff[r] = (min(max(y0 - 1 + r, 0), H - 1) * W + col) * 4;
+        if (EDGE) eoff[r] = (ledge || redge) ? roff[r] + ecol * 4 : __builtin_amdgcn_readfirstlane(roff[r]);
+    }
 
     // bilinear sources of the 2 x 2 pixels (align_corners=True).  The launcher has checked that the first source of an odd row /
     // column is one of the two sources of the even one before it (the second, except in the first pair where both start at 0), so
@@ -104,36 +118,41 @@ __global__ __launch_bounds__(256) void decoder_merge_kernel(DmParams a, DmGeom g
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) boff[r * 3 + c] = rr[r] + cc[c];
+            for (int c = 0; c < 3; ++c) boff[r * 3 + c] = (rr[r] + cc[c]) * 4;
     }
     const int G = g.Cout / COB;
     const size_t hw = (size_t)H * W, hwi = (size_t)Hi * Wi;
-    const float* encn = a.enc + (size_t)n * g.Cin * hw;
-    const float* bun = a.bu + (size_t)n * g.Cout * hwi;
+    const int hwb = H * W * 4, hwib = Hi * Wi * 4;                  // bytes of a plane (the launcher bounds an image's bytes)
+    // one descriptor per tensor, over this wave's image: every address below is clamped in range, the range check is a safety net
+    const __amdgpu_buffer_rsrc_t ers =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.enc + (size_t)n * g.Cin * hw), 0, g.Cin * hwb, 0x00020000);
+    const __amdgpu_buffer_rsrc_t brs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bu + (size_t)n * g.Cout * hwi), 0, g.Cout * hwib, 0x00020000);
     const float* gaten = a.gate + (size_t)n * g.Cout;
 
-    struct RawC { float2 row[CH][4]; float edge[CH][4]; };
+    struct RawC { float2 row[CH][4]; float edge[EDGE ? CH : 1][4]; };
     struct RawB { float s[COB][9]; };
     auto load_c = [&](int q, RawC& rc) {                            // q: chunk of CH input channels
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
-            const float* xp = encn + (size_t)(q * CH + i) * hw;
+            const int so = (q * CH + i) * hwb;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) rc.row[i][r] = *reinterpret_cast<const float2*>(xp + roff[r]);
+            for (int r = 0; r < 4; ++r) {
+                const dm_u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(ers, roff[r], so, 0);
+                rc.row[i][r] = make_float2(__uint_as_float(t.x), __uint_as_float(t.y));
+            }
+            if constexpr (EDGE) {                                   // read under ledge / redge only
 #pragma unroll
-            for (int r = 0; r < 4; ++r) rc.edge[i][r] = 0.f;
-            if (ledge || redge) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) rc.edge[i][r] = xp[roff[r] + ecol];
+                for (int r = 0; r < 4; ++r) rc.edge[i][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ers, eoff[r], so, 0));
             }
         }
     };
     auto load_b = [&](int grp, RawB& rb) {
 #pragma unroll
         for (int c = 0; c < COB; ++c) {
-            const float* bp = bun + (size_t)(grp * COB + c) * hwi;
+            const int so = (grp * COB + c) * hwib;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) rb.s[c][k] = bp[boff[k]];
+            for (int k = 0; k < 9; ++k) rb.s[c][k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(brs, boff[k], so, 0));
         }
     };
 
@@ -143,72 +162,57 @@ __global__ __launch_bounds__(256) void decoder_merge_kernel(DmParams a, DmGeom g
 #pragma unroll
         for (int t = 0; t < 2; ++t) pacc[p][t][0] = pacc[p][t][1] = 0.f;
 
-    RawC ccur, cnxt;
-    RawB bcur, bnxt;
-    const int g0 = ws * (G / SPLIT), g1 = g0 + G / SPLIT;           // G % SPLIT == 0 (launcher)
-    load_c(g0 * NCH, ccur);
-    load_b(g0, bcur);
-    const int Q = g.Cin / CH;
-#pragma unroll 1
-    for (int grp = g0; grp < g1; ++grp) {
-        load_b(min(grp + 1, G - 1), bnxt);
-        const float* wg = w3s + grp * COB * CG * 9;
-        float acc[COB][2][2];
+    // the 3x3 taps of one chunk of CH input channels (chunk cc of its group) into acc
+    auto conv_chunk = [&](const RawC& rc, const float* wg, int cc, float (&acc)[COB][2][2]) {
+        // input row r of channel i feeds output row 0 through kernel row r and output row 1 through kernel row r - 1
+        auto feed = [&](int i, int r) {
+            float2 v = rc.row[i][r];
+            float ev = EDGE ? rc.edge[i][r] : 0.f;
+            const bool rin = r == 0 ? top_in : (r == 3 ? bot_in : true);
+            if (!rin) { v.x = 0.f; v.y = 0.f; ev = 0.f; }
+            float win[4];
+            win[1] = v.x;  win[2] = v.y;
+            const float fl = dm_from_left(v.y), fr = dm_from_right(v.x);
+            win[0] = lok ? fl : (ledge ? ev : 0.f);
+            win[3] = rok ? fr : (redge ? ev : 0.f);
+            const int ci = cc * CH + i;
 #pragma unroll
-        for (int c = 0; c < COB; ++c)
+            for (int t = 0; t < 2; ++t) {
+                const int ky = r - t;
+                if (ky < 0 || ky > 2) continue;
 #pragma unroll
-            for (int t = 0; t < 2; ++t) acc[c][t][0] = acc[c][t][1] = 0.f;
-#pragma unroll 1
-        for (int cc = 0; cc < NCH; ++cc) {                          // (unrolled 8 x 27 weights overflow the scalar registers)
-            load_c(min(grp * NCH + cc + 1, Q - 1), cnxt);
-            // input row r of channel i feeds output row 0 through kernel row r and output row 1 through kernel row r - 1
-            auto feed = [&](int i, int r) {
-                float2 v = ccur.row[i][r];
-                float ev = ccur.edge[i][r];
-                const bool rin = r == 0 ? top_in : (r == 3 ? bot_in : true);
-                if (!rin) { v.x = 0.f; v.y = 0.f; ev = 0.f; }
-                float win[4];
-                win[1] = v.x;  win[2] = v.y;
-                const float fl = dm_from_left(v.y), fr = dm_from_right(v.x);
-                win[0] = lok ? fl : (ledge ? ev : 0.f);
-                win[3] = rok ? fr : (redge ? ev : 0.f);
-                const int ci = cc * CH + i;
+                for (int c = 0; c < COB; ++c) {
+                    const float* wk = wg + (c * CG + ci) * 9 + ky * 3;
+                    const float w0 = wk[0], w1 = wk[1], w2 = wk[2];
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int ky = r - t;
-                    if (ky < 0 || ky > 2) continue;
-#pragma unroll
-                    for (int c = 0; c < COB; ++c) {
-                        const float* wk = wg + (c * CG + ci) * 9 + ky * 3;
-                        const float w0 = wk[0], w1 = wk[1], w2 = wk[2];
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            acc[c][t][j] = fmaf(w0, win[j], acc[c][t][j]);
-                            acc[c][t][j] = fmaf(w1, win[j + 1], acc[c][t][j]);
-                            acc[c][t][j] = fmaf(w2, win[j + 2], acc[c][t][j]);
-                        }
+                    for (int j = 0; j < 2; ++j) {
+                        acc[c][t][j] = fmaf(w0, win[j], acc[c][t][j]);
+                        acc[c][t][j] = fmaf(w1, win[j + 1], acc[c][t][j]);
+                        acc[c][t][j] = fmaf(w2, win[j + 2], acc[c][t][j]);
                     }
                 }
-            };
-            if (KYOUT) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int i = 0; i < CH; ++i) feed(i, r);
-            } else {
-#pragma unroll
-                for (int i = 0; i < CH; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) feed(i, r);
             }
-            ccur = cnxt;
+        };
+        if (KYOUT) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int i = 0; i < CH; ++i) feed(i, r);
+        } else {
+#pragma unroll
+            for (int i = 0; i < CH; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) feed(i, r);
         }
+    };
+    // both epilogues, the blend and the projection of one group's COB output channels
+    auto finish = [&](int grp, const RawB& rb, const float (&acc)[COB][2][2]) {
 #pragma unroll
         for (int c = 0; c < COB; ++c) {
             const int co = grp * COB + c;
             const float es = a.e_scale[co], eb = a.e_shift[co], ea = a.e_alpha[co], gt = gaten[co];
             const float bs = a.b_scale[co], bb = a.b_shift[co], ba = a.b_alpha[co];
-            const float* s = bcur.s[c];
+            const float* s = rb.s[c];
             float h[3][2];
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
@@ -245,7 +249,62 @@ __global__ __launch_bounds__(256) void decoder_merge_kernel(DmParams a, DmGeom g
                 }
             }
         }
-        bcur = bnxt;
+    };
+
+    // Two named buffers for the fetched input rows: a step computes from one while the other loads and the next step swaps the
+    // names, so nothing is copied at a back edge.  The prefetch past the last chunk / group is clamped to the last one (in bounds,
+    // unused).
+    const int g0 = ws * (G / SPLIT), g1 = g0 + G / SPLIT;           // G % SPLIT == 0 (launcher)
+    const int Q = g.Cin / CH;
+    static_assert(NCH == 1 || NCH % 2 == 0, "the channel loop runs in pairs of chunks");
+    RawC c0, c1;
+    load_c(g0 * NCH, c0);
+    if constexpr (NCH == 1) {
+        // one chunk per group: the group loop itself is the two-step body, the low-resolution samples are double-buffered with
+        // the rows (a group is too short to hide their latency behind itself)
+        auto group = [&](int grp, const RawC& ccur, RawC& cnxt, const RawB& bcur, RawB& bnxt) {
+            load_b(min(grp + 1, G - 1), bnxt);
+            load_c(min(grp + 1, Q - 1), cnxt);
+            float acc[COB][2][2];
+#pragma unroll
+            for (int c = 0; c < COB; ++c)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[c][t][0] = acc[c][t][1] = 0.f;
+            conv_chunk(ccur, w3s + grp * COB * CG * 9, 0, acc);
+            finish(grp, bcur, acc);
+        };
+        RawB b0, b1;
+        load_b(g0, b0);
+#pragma unroll 1
+        for (int grp = g0;;) {                                      // an odd trip count leaves after the first step (uniform)
+            group(grp, c0, c1, b0, b1);
+            if (++grp == g1) break;
+            group(grp, c1, c0, b1, b0);
+            if (++grp == g1) break;
+        }
+    } else {
+        // NCH chunks per group, walked in pairs: c0 holds the group's first chunk on entry and the next group's on exit.  The
+        // group's low-resolution samples are requested when the group starts and used after its 3x3 loop, which hides them: one
+        // buffer, nothing to copy.
+#pragma unroll 1
+        for (int grp = g0; grp < g1; ++grp) {
+            RawB b;
+            load_b(grp, b);
+            const float* wg = w3s + grp * COB * CG * 9;
+            float acc[COB][2][2];
+#pragma unroll
+            for (int c = 0; c < COB; ++c)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[c][t][0] = acc[c][t][1] = 0.f;
+#pragma unroll 1
+            for (int cc = 0; cc < NCH; cc += 2) {                   // (unrolled 8 x 27 weights overflow the scalar registers)
+                load_c(grp * NCH + cc + 1, c1);
+                conv_chunk(c0, wg, cc, acc);
+                load_c(min(grp * NCH + cc + 2, Q - 1), c0);
+                conv_chunk(c1, wg, cc + 1, acc);
+            }
+            finish(grp, b, acc);
+        }
     }
     if (SPLIT > 1) {                                                // partial sums of waves 1 .. SPLIT-1 -> LDS, added by wave 0 in wave order
         float* red = w3s + g.Cout * CG * 9;                         // [SPLIT - 1][P * 4][64]
@@ -298,18 +357,24 @@ static bool dm_sources_pair_up(float scale, int in_size, int out_size) {
     return true;
 }
 
-template <int CG, int COB, bool KYOUT, int SPLIT>
-static int dm_launch_split(const DmParams& a, const DmGeom& g, int P, float* out, hipStream_t s) {
+template <int CG, int COB, bool KYOUT, int SPLIT, bool EDGE>
+static int dm_launch_edge(const DmParams& a, const DmGeom& g, int P, float* out, hipStream_t s) {
     const dim3 grid(SPLIT == 1 ? (unsigned)ceil_div64((int64_t)g.total, 4) : g.total), blk(256);
     const size_t lds = ((size_t)g.Cout * (DM_PS + CG * 9) + (size_t)(SPLIT - 1) * P * 4 * 64) * sizeof(float);
     switch (P) {
-        case 16: hipLaunchKernelGGL((decoder_merge_kernel<CG, COB, 16, KYOUT, SPLIT>), grid, blk, lds, s, a, g, out); break;
-        case 10: hipLaunchKernelGGL((decoder_merge_kernel<CG, COB, 10, KYOUT, SPLIT>), grid, blk, lds, s, a, g, out); break;
-        case 6: hipLaunchKernelGGL((decoder_merge_kernel<CG, COB, 6, KYOUT, SPLIT>), grid, blk, lds, s, a, g, out); break;
-        case 2: hipLaunchKernelGGL((decoder_merge_kernel<CG, COB, 2, KYOUT, SPLIT>), grid, blk, lds, s, a, g, out); break;
+        case 16: hipLaunchKernelGGL((decoder_merge_kernel<CG, COB, 16, KYOUT, SPLIT, EDGE>), grid, blk, lds, s, a, g, out); break;
+        case 10: hipLaunchKernelGGL((decoder_merge_kernel<CG, COB, 10, KYOUT, SPLIT, EDGE>), grid, blk, lds, s, a, g, out); break;
+        case 6: hipLaunchKernelGGL((decoder_merge_kernel<CG, COB, 6, KYOUT, SPLIT, EDGE>), grid, blk, lds, s, a, g, out); break;
+        case 2: hipLaunchKernelGGL((decoder_merge_kernel<CG, COB, 2, KYOUT, SPLIT, EDGE>), grid, blk, lds, s, a, g, out); break;
         default: return 1;
     }
     return 0;
+}
+
+// rows wider than 128 columns are cut into column blocks (a geometry of the map alone): the form that loads the blocks' halo columns
+template <int CG, int COB, bool KYOUT, int SPLIT>
+static int dm_launch_split(const DmParams& a, const DmGeom& g, int P, float* out, hipStream_t s) {
+    return g.ncb > 1 ? dm_launch_edge<CG, COB, KYOUT, SPLIT, true>(a, g, P, out, s) : dm_launch_edge<CG, COB, KYOUT, SPLIT, false>(a, g, P, out, s);
 }
 
 // Four waves per tile for the grouped shapes (8 -> 3, 4 -> 1: a wave's walk over all groups is long and their maps are small:
@@ -330,6 +395,8 @@ static int decoder_merge_try(const DmParams& a, int N, int Cin, int Cout, int P,
     if ((H & 1) || (W & 1) || H < 2 || W < 2 || !(P == 2 || P == 6 || P == 10 || P == 16)) return 1;
     if (!al16(a.enc) || !al16(a.bu) || !al16(out) || !al16(a.w3)) return 1;
     if ((int64_t)N * Cin * H * W >= (1ll << 31) || (int64_t)N * Cout * H * W >= (1ll << 31) || Cout > 1024) return 1;
+    // the kernel addresses an image of enc / bu through a buffer descriptor: 32-bit byte offsets and a 32-bit byte count per image
+    if ((int64_t)Cin * H * W * 4 >= (1ll << 31) || (int64_t)Cout * (H / 2) * (W / 2) * 4 >= (1ll << 31)) return 1;
     int G = Cin, r = Cout;                                         // groups = gcd(Cin, Cout), nn_layers/efficient_pt.py:19
     while (r) { const int t = G % r; G = r; r = t; }
     const int cg = Cin / G, cob = Cout / G;
