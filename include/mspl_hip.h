@@ -107,6 +107,55 @@ int mspl_eesp_dw_hff_fwd(const float* x, const float* w, const int32_t dil[4], i
 int mspl_conv1x1_fwd(const float* x, const float* w, int32_t N, int32_t Cin, int32_t Cout,
                      int32_t groups, int32_t HW, const mspl_epilogue_t* ep, float* out, void* stream);
 
+/* The kernel form mspl_conv1x1_fwd takes for a call, with the parameters that select an instantiation or bound a loop, the dynamic
+ *     LDS and the grid.  Host only, no device call, no state: it returns what the one host function the launcher itself switches on
+ *     returns, and a shape the launcher refuses is refused here with the launcher's error code and text.
+ *     out_ctot: channels of the destination (0: Cout).  terms: MSPL_PW_TERM_* of the epilogue operands present (the split-K form
+ *     takes scale / shift / alpha / raw_out only).  *_align: the largest power of two, at most 16, that divides the address of
+ *     x / w / out; operand_align: the smallest of pre_add, residual and reinf_r (the per-pixel operands the matrix-core forms read
+ *     with vector loads); side_align: the smallest of raw_out and gate (the thin form alone asks for them); 16 where none is
+ *     present.  out: MSPL_PW_PLAN_LEN entries; what does not apply to the form is 0.  (Tuning variables are not seen here.)
+ *     Split-K rule: M <= 32, ungrouped, K >= 4M, K % 64 == 0 -- each of the four waves walks K/4 in chunks of 2*CH k without a tail,
+ *     so KS % (2*CH) == 0 must hold; other K (96, 160, 224, ...) take the tile-pipelined or the LDS-ring form. */
+typedef enum {
+    MSPL_PW_FORM_THIN = 1,               /* vector unit, one float4 of pixels per lane, M <= 16, K % 8 == 0, large maps */
+    MSPL_PW_FORM_SMALL_K = 2,            /* vector unit, K < 16 or odd K, weights in LDS (<= 48 KiB) */
+    MSPL_PW_FORM_SPLIT_K = 3,            /* matrix cores, four waves split K */
+    MSPL_PW_FORM_TILE_PIPELINED = 4,     /* matrix cores, K = 8 * NG */
+    MSPL_PW_FORM_REGISTER_WEIGHTS = 5,   /* matrix cores, weights in registers (reachable through a tuning variable only) */
+    MSPL_PW_FORM_LDS_RING = 6            /* matrix cores, weights in LDS padded to 32 columns, any even K */
+} mspl_conv1x1_form_t;
+#define MSPL_PW_TERM_SCALE 1
+#define MSPL_PW_TERM_SHIFT 2
+#define MSPL_PW_TERM_ALPHA 4
+#define MSPL_PW_TERM_PRE_ADD 8
+#define MSPL_PW_TERM_RESIDUAL 16
+#define MSPL_PW_TERM_REINF 32
+#define MSPL_PW_TERM_GATE 64
+#define MSPL_PW_TERM_RAW_OUT 128
+#define MSPL_PW_PLAN_FORM 0             /* an mspl_conv1x1_form_t */
+#define MSPL_PW_PLAN_MT 1               /* thin: 8 / 16, small-K: 2 / 4 / 8 -- output rows per thread (the instantiation) */
+#define MSPL_PW_PLAN_MTILES 2           /* thin, small-K: row tiles per group */
+#define MSPL_PW_PLAN_NSUB 3             /* matrix-core forms: pixels per lane (split-K: 32-pixel sub-tiles per workgroup) */
+#define MSPL_PW_PLAN_CH 4               /* split-K: MFMA steps per chunk (8 / 16) */
+#define MSPL_PW_PLAN_KS 5               /* split-K: k per wave; other matrix-core forms: LDS row stride of the weights */
+#define MSPL_PW_PLAN_TILES 6            /* split-K: pixel tiles per image */
+#define MSPL_PW_PLAN_NG 7               /* tile-pipelined / register-weights: K / 8 of the instantiation */
+#define MSPL_PW_PLAN_MB 8               /* matrix-core forms but split-K: output rows per workgroup */
+#define MSPL_PW_PLAN_AR 9               /* tile-pipelined: weight rows staged */
+#define MSPL_PW_PLAN_WM 10              /* matrix-core forms but split-K: waves along M */
+#define MSPL_PW_PLAN_TPW 11             /* ... pixel tiles per wave */
+#define MSPL_PW_PLAN_RING 12            /* LDS-ring: B groups in flight per wave */
+#define MSPL_PW_PLAN_VECW 13            /* matrix-core forms but split-K: 1 = 16-byte weight staging, 0 = scalar */
+#define MSPL_PW_PLAN_LDS_BYTES 14       /* dynamic LDS of the launch */
+#define MSPL_PW_PLAN_GRID_X 15
+#define MSPL_PW_PLAN_GRID_Y 16
+#define MSPL_PW_PLAN_GRID_Z 17
+#define MSPL_PW_PLAN_LEN 18
+int mspl_conv1x1_fwd_plan(int32_t N, int32_t Cin, int32_t Cout, int32_t groups, int32_t HW, int32_t out_ctot, uint32_t terms,
+                          int32_t x_align, int32_t w_align, int32_t out_align, int32_t operand_align, int32_t side_align,
+                          int32_t* out);
+
 /* Generic grouped 3x3 convolution, padding 1, dilation 1, stride 1 or 2 (direct, LDS-tiled) + epilogue.
  *     Replaces model/classification/espnetv2.py:61 (level1 stem), nn_layers/eesp.py:118 (inp_reinf.0),
  *     efficient_pyramid_pool.py:24 (depthwise stages), :30 (merge CBR), efficient_pt.py:21 (expansion).

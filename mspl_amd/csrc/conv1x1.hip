@@ -20,12 +20,9 @@
 
 #include <mutex>
 
-#include "common.hpp"
+#include "conv1x1_plan.hpp"
 
 namespace mspl {
-
-int conv1x1_splitk_try(const float* x, const float* w, int N, int Cin, int Cout, int groups, int HW, const Epi& e, float* out,
-                       hipStream_t s);
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -829,38 +826,76 @@ __global__ __launch_bounds__(256) void conv1x1_thin_kernel(const float* __restri
     }
 }
 
-// 0 = launched.  Shapes: M <= 16 per group, K in 8..64 (multiple of 8), planes a multiple of 4 pixels, >= 400 workgroups.
-static int launch_thin_try(const float* x, const float* w, int N, int Cin, int Cout, int groups, int HW, const Epi& e, float* out,
-                           hipStream_t s) {
+// ------------------------------------------------------------------ the host decision
+// Everything the dispatch of mspl_conv1x1_fwd reads: the shape, whether the epilogue is lean, and the alignment of the pointers.
+// mspl_conv1x1_fwd fills it from its arguments, mspl_conv1x1_fwd_plan from what the caller states.
+struct PwFacts {
+    int N, Cin, Cout, G, HW, ctot;
+    bool lean;                 // no pre_add / residual / reinforcement / gate
+    // largest power of two (<= 16) dividing the address; 16 for an absent pointer
+    int ax, aw, aout;          // x, w, out
+    int aop;                   // the per-pixel operands the matrix-core forms read with vector loads: pre_add, residual, reinf_r
+    int aside;                 // raw_out and gate (the thin form alone looks at them)
+};
+
+static inline int pw_align(const void* p) {
+    const uintptr_t a = (uintptr_t)p | 16;
+    return (int)(a & (~a + 1));
+}
+
+// What pw_decide answers: the form (an mspl_conv1x1_form_t), its geometry struct, the instantiation, the dynamic LDS and the grid.
+struct PwPlan {
+    int form;
+    PwGeom g;                  // tile-pipelined / register-weights / LDS-ring
+    PwSmall sg;                // thin / small-K vector
+    SkPlan sk;                 // split-K
+    int mt;                    // thin: 8 / 16; small-K vector: 2 / 4 / 8
+    int nsub;                  // matrix-core forms: pixels per lane (1, 2, 4)
+    int ng;                    // tile-pipelined / register-weights: K / 8 of the instantiation
+    int ring;                  // LDS-ring: B groups in flight per wave
+    size_t lds;
+    unsigned gx, gy, gz;
+};
+
+// pixels per lane a shape and its pointers allow (vector loads of ns floats)
+static inline bool pw_vec_ok(const PwFacts& f, int ns) {
+    const int a = ns * 4;
+    return f.HW % ns == 0 && f.ax >= a && f.aout >= a && f.aop >= a;
+}
+
+// 0 = the thin form takes it.  Shapes: M <= 16 per group, K in 8..64 (multiple of 8), planes a multiple of 4 pixels, >= 400 workgroups.
+static int plan_thin(const PwFacts& f, PwPlan& p) {
     static const int enabled = MSPL_TUNE_INT("MSPL_PW_THIN", 1);
-    const int K = Cin / groups, M = Cout / groups;
+    const int K = f.Cin / f.G, M = f.Cout / f.G;
     // measured (tools/bench_ops.py, bs 16): 32 -> 16 at 144x240 26.1 -> 23.0 us, 16 -> 13 18.3 -> 15.6, 128 -> 32 g4 at 72x120
     // 23.9 -> 18.9; with fewer than ~2 workgroups per CU (48 -> 16 at 72x120: 144) the MFMA kernel's finer tiles win (13 vs 20 us)
-    if (!enabled || M > 16 || K < 8 || K > 64 || (K & 7) != 0 || (HW & 3) != 0 ||
-        (int64_t)N * groups * ceil_div(HW / 4, 256) < 400)
+    if (!enabled || M > 16 || K < 8 || K > 64 || (K & 7) != 0 || (f.HW & 3) != 0 ||
+        (int64_t)f.N * f.G * ceil_div(f.HW / 4, 256) < 400)
         return 1;
-    if (((uintptr_t)x & 15) || ((uintptr_t)out & 15) || ((uintptr_t)e.raw & 15) || ((uintptr_t)e.pre_add & 15) ||
-        ((uintptr_t)e.residual & 15) || ((uintptr_t)e.reinf_r & 15) || ((uintptr_t)e.gate & 15))
-        return 1;
-    PwSmall g;
-    g.N = N; g.Cin = Cin; g.Cout = Cout; g.G = groups; g.K = K; g.M = M; g.HW = HW;
-    g.Q = HW / 4;
+    if (f.ax < 16 || f.aout < 16 || f.aop < 16 || f.aside < 16) return 1;
+    PwSmall& g = p.sg;
+    g.N = f.N; g.Cin = f.Cin; g.Cout = f.Cout; g.G = f.G; g.K = K; g.M = M; g.HW = f.HW;
+    g.Q = f.HW / 4;
     g.mtiles = 1;
-    const int mt = M <= 8 ? 8 : 16;
-    const size_t lds = (size_t)groups * K * mt * sizeof(float);
-    if (lds > 48 * 1024) return 1;
-    const int64_t slabs = (int64_t)N * groups;
+    p.mt = M <= 8 ? 8 : 16;
+    p.lds = (size_t)f.G * K * p.mt * sizeof(float);
+    if (p.lds > 48 * 1024) return 1;
+    const int64_t slabs = (int64_t)f.N * f.G;
     if (slabs >= 65535ll * 65535ll) return 1;
     const int gy = slabs < 65535 ? (int)slabs : 65535;
-    dim3 grid((unsigned)ceil_div(g.Q, 256), (unsigned)gy, (unsigned)ceil_div64(slabs, gy)), blk(256);
-    if (mt == 8) hipLaunchKernelGGL((conv1x1_thin_kernel<8, 8>), grid, blk, lds, s, x, w, g, e, out);
-    else hipLaunchKernelGGL((conv1x1_thin_kernel<16, 8>), grid, blk, lds, s, x, w, g, e, out);
+    p.gx = (unsigned)ceil_div(g.Q, 256); p.gy = (unsigned)gy; p.gz = (unsigned)ceil_div64(slabs, gy);
     return 0;
 }
 
-// Launch of the tile-pipelined kernel (K % 32 == 0 or K in {16, 24}, aligned weights, small feature maps).
-static int launch_pipe(const float* x, const float* w, PwGeom g, const Epi& e, const mspl_epilogue_t* ep, float* out,
-                       hipStream_t s) {
+static void launch_thin(const float* x, const float* w, const PwPlan& p, const Epi& e, float* out, hipStream_t s) {
+    const dim3 grid(p.gx, p.gy, p.gz), blk(256);
+    if (p.mt == 8) hipLaunchKernelGGL((conv1x1_thin_kernel<8, 8>), grid, blk, p.lds, s, x, w, p.sg, e, out);
+    else hipLaunchKernelGGL((conv1x1_thin_kernel<16, 8>), grid, blk, p.lds, s, x, w, p.sg, e, out);
+}
+
+// Plan of the tile-pipelined kernel (K % 32 == 0 or K in {16, 24}, aligned weights, small feature maps).
+static int plan_pipe(const PwFacts& f, PwPlan& p) {
+    PwGeom& g = p.g;
     g.KS = g.K | 1;
     int mbr = ((g.M + 31) / 32) * 32;
     if (mbr > 128) mbr = 128;
@@ -872,15 +907,11 @@ static int launch_pipe(const float* x, const float* w, PwGeom g, const Epi& e, c
     g.mc_total = mbr / 32;
     g.WM = g.mc_total >= 3 ? 4 : g.mc_total;
     const int wp = 4 / g.WM;
-    auto al = [](const void* p, int a) { return p == nullptr || (((uintptr_t)p) & (a - 1)) == 0; };
-    auto ok = [&](int ns) {
-        const int a = ns * 4;
-        return g.HW % ns == 0 && al(x, a) && al(out, a) && (!ep || (al(ep->pre_add, a) && al(ep->residual, a) && al(ep->reinf_r, a)));
-    };
-    int nsub = ok(2) ? 2 : 1;
+    int nsub = pw_vec_ok(f, 2) ? 2 : 1;
     static const int dbg_nsub = MSPL_TUNE_INT("MSPL_PW_NSUB", 0);
     static const int dbg_tpw = MSPL_TUNE_INT("MSPL_PW_TPW", 0);
-    if ((dbg_nsub == 1 || dbg_nsub == 2) && ok(dbg_nsub)) nsub = dbg_nsub;
+    if ((dbg_nsub == 1 || dbg_nsub == 2) && pw_vec_ok(f, dbg_nsub)) nsub = dbg_nsub;
+    p.nsub = nsub;
     g.ptiles = (int)ceil_div64((int64_t)g.N * g.HW, 32 * nsub);
     // workgroups: at most one resident round (3 per CU), each walking TPW tiles per wave
     int tpw = 1;
@@ -891,16 +922,28 @@ static int launch_pipe(const float* x, const float* w, PwGeom g, const Epi& e, c
     g.pgroups = ceil_div(g.ptiles, wp * tpw);
     const int64_t blocks = (int64_t)g.G * g.mblocks * g.pgroups;
     MSPL_REQUIRE(blocks < (1ll << 31), MSPL_ERR_BAD_SHAPE, "conv1x1: grid too large");
-    const dim3 grid((unsigned)blocks), blk(256);
+    p.gx = (unsigned)blocks; p.gy = p.gz = 1;
+    g.AR = g.M < g.MB ? g.M : g.MB;
+    p.lds = ((size_t)g.MB * ROWC + (size_t)g.AR * g.KS) * sizeof(float);
+    MSPL_REQUIRE(p.lds <= 96 * 1024, MSPL_ERR_UNSUPPORTED, "conv1x1: weight tile of %zu B exceeds LDS", p.lds);
+    const int ng8 = g.K >> 3;                                // the instantiation: pw_decide admits 2, 3, 4, 6, 8, 12, 16, 32, 64
+    p.ng = (ng8 == 2 || ng8 == 3 || ng8 == 4 || ng8 == 6 || ng8 == 8 || ng8 == 12 || ng8 == 16 || ng8 == 32) ? ng8 : 64;
+    return MSPL_OK;
+}
+
+// Launch of the tile-pipelined kernel as planned.
+static int launch_pipe(const float* x, const float* w, const PwPlan& p, const Epi& e, float* out, hipStream_t s) {
+    PwGeom g = p.g;
+    const int nsub = p.nsub;
+    const size_t lds = p.lds;
+    const int64_t blocks = p.gx;
+    const dim3 grid(p.gx), blk(256);
     {
         static unsigned long long* stamp_buf = nullptr;
         static const int dbg_stamp = MSPL_STAMP_ENV("MSPL_PW_STAMP");
         if (dbg_stamp && !stamp_buf) (void)hipMalloc(&stamp_buf, (size_t)5 * 65536 * sizeof(unsigned long long));
         g.stamps = (dbg_stamp && blocks <= 65536) ? stamp_buf : nullptr;
     }
-    g.AR = g.M < g.MB ? g.M : g.MB;
-    const size_t lds = ((size_t)g.MB * ROWC + (size_t)g.AR * g.KS) * sizeof(float);
-    MSPL_REQUIRE(lds <= 96 * 1024, MSPL_ERR_UNSUPPORTED, "conv1x1: weight tile of %zu B exceeds LDS", lds);
     if (lds > 64 * 1024) {
 #define MSPL_PIPE_ATTR(NG) do { (void)hipFuncSetAttribute((const void*)conv1x1_pipe_kernel<2, NG>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
                                 (void)hipFuncSetAttribute((const void*)conv1x1_pipe_kernel<1, NG>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); } while (0)
@@ -910,7 +953,7 @@ static int launch_pipe(const float* x, const float* w, PwGeom g, const Epi& e, c
     }
 #define MSPL_PIPE(NG) do { if (nsub == 2) hipLaunchKernelGGL((conv1x1_pipe_kernel<2, NG>), grid, blk, lds, s, x, w, g, e, out); \
                            else hipLaunchKernelGGL((conv1x1_pipe_kernel<1, NG>), grid, blk, lds, s, x, w, g, e, out); } while (0)
-    switch (g.K >> 3) {
+    switch (p.ng) {
         case 2: MSPL_PIPE(2); break;
         case 3: MSPL_PIPE(3); break;
         case 4: MSPL_PIPE(4); break;
@@ -936,9 +979,9 @@ static int launch_pipe(const float* x, const float* w, PwGeom g, const Epi& e, c
     return MSPL_OK;
 }
 
-// Launch of the register-resident-weights kernel (K % 8 == 0, K <= 128, aligned weights).
-static int launch_areg(const float* x, const float* w, PwGeom g, const Epi& e, const mspl_epilogue_t* ep, float* out,
-                       hipStream_t s) {
+// Plan of the register-resident-weights kernel (K % 8 == 0, K <= 128, aligned weights).
+static int plan_areg(const PwFacts& f, PwPlan& p) {
+    PwGeom& g = p.g;
     static const int dbg_astage = MSPL_TUNE_INT("MSPL_PW_ASTAGE", -1);
     g.astage = dbg_astage >= 0 ? dbg_astage : !(g.K <= 32 && (int64_t)g.N * g.HW >= 100000);
     g.KS = g.K | 1;
@@ -951,18 +994,14 @@ static int launch_areg(const float* x, const float* w, PwGeom g, const Epi& e, c
     g.mc_total = mbr / 32;
     g.WM = g.mc_total >= 3 ? 4 : g.mc_total;
     const int wp = 4 / g.WM;
-    auto al = [](const void* p, int a) { return p == nullptr || (((uintptr_t)p) & (a - 1)) == 0; };
-    auto ok = [&](int ns) {
-        const int a = ns * 4;
-        return g.HW % ns == 0 && al(x, a) && al(out, a) && (!ep || (al(ep->pre_add, a) && al(ep->residual, a) && al(ep->reinf_r, a)));
-    };
     // wave tiles = groups x 32-row chunks x pixel tiles; aim at >= 4 per SIMD (1024 SIMDs) for balance
     auto tiles_of = [&](int ns) { return (int64_t)g.G * g.mblocks * g.mc_total * ceil_div64((int64_t)g.N * g.HW, 32 * ns); };
     int nsub = 1;
-    if (ok(2) && tiles_of(2) >= 4096) nsub = 2;
+    if (pw_vec_ok(f, 2) && tiles_of(2) >= 4096) nsub = 2;
     static const int dbg_nsub = MSPL_TUNE_INT("MSPL_PW_NSUB", 0);   // tuning override
     static const int dbg_tpw = MSPL_TUNE_INT("MSPL_PW_TPW", 0);
-    if ((dbg_nsub == 1 || dbg_nsub == 2) && ok(dbg_nsub)) nsub = dbg_nsub;
+    if ((dbg_nsub == 1 || dbg_nsub == 2) && pw_vec_ok(f, dbg_nsub)) nsub = dbg_nsub;
+    p.nsub = nsub;
     g.ptiles = (int)ceil_div64((int64_t)g.N * g.HW, 32 * nsub);
     int tpw = 1;
     while (tpw < 8 && tiles_of(nsub) / (tpw * 2) >= 4096) tpw *= 2;      // keep >= 4 waves per SIMD
@@ -971,11 +1010,22 @@ static int launch_areg(const float* x, const float* w, PwGeom g, const Epi& e, c
     g.pgroups = ceil_div(g.ptiles, wp * tpw);
     const int64_t blocks = (int64_t)g.G * g.mblocks * g.pgroups;
     MSPL_REQUIRE(blocks < (1ll << 31), MSPL_ERR_BAD_SHAPE, "conv1x1: grid too large");
-    const dim3 grid((unsigned)blocks), blk(256);
-    const size_t lds = (size_t)g.MB * (ROWC + (g.astage ? g.KS : 0)) * sizeof(float);
+    p.gx = (unsigned)blocks; p.gy = p.gz = 1;
+    p.lds = (size_t)g.MB * (ROWC + (g.astage ? g.KS : 0)) * sizeof(float);
+    const int ng8 = g.K >> 3;                                // the instantiation: pw_decide admits 2, 3, 4, 6, 8, 12, 16
+    p.ng = (ng8 == 2 || ng8 == 3 || ng8 == 4 || ng8 == 6 || ng8 == 8 || ng8 == 12) ? ng8 : 16;
+    return MSPL_OK;
+}
+
+// Launch of the register-resident-weights kernel as planned.
+static int launch_areg(const float* x, const float* w, const PwPlan& p, const Epi& e, float* out, hipStream_t s) {
+    const PwGeom& g = p.g;
+    const int nsub = p.nsub;
+    const size_t lds = p.lds;
+    const dim3 grid(p.gx), blk(256);
 #define MSPL_AREG(NG) do { if (nsub == 2) hipLaunchKernelGGL((conv1x1_areg_kernel<2, NG>), grid, blk, lds, s, x, w, g, e, out); \
                            else hipLaunchKernelGGL((conv1x1_areg_kernel<1, NG>), grid, blk, lds, s, x, w, g, e, out); } while (0)
-    switch (g.K >> 3) {
+    switch (p.ng) {
         case 2: MSPL_AREG(2); break;
         case 3: MSPL_AREG(3); break;
         case 4: MSPL_AREG(4); break;
@@ -993,54 +1043,60 @@ static int launch_areg(const float* x, const float* w, PwGeom g, const Epi& e, c
 
 using namespace mspl;
 
-static int launch_small(const float* x, const float* w, int N, int Cin, int Cout, int groups, int HW,
-                        const Epi& e, float* out, hipStream_t s) {
-    PwSmall g;
-    g.N = N; g.Cin = Cin; g.Cout = Cout; g.G = groups; g.K = Cin / groups; g.M = Cout / groups; g.HW = HW;
-    g.Q = ceil_div(HW, 4);
-    const int mt = g.M <= 2 ? 2 : (g.M <= 4 ? 4 : 8);
-    g.mtiles = ceil_div(g.M, mt);
-    const size_t lds = (size_t)Cout * g.K * sizeof(float);
-    MSPL_REQUIRE(lds <= 48 * 1024, MSPL_ERR_UNSUPPORTED, "conv1x1(small-K): weight block %zu B exceeds LDS", lds);
-    const int64_t slabs = (int64_t)N * groups * g.mtiles;
+static int plan_small(const PwFacts& f, PwPlan& p) {
+    PwSmall& g = p.sg;
+    g.N = f.N; g.Cin = f.Cin; g.Cout = f.Cout; g.G = f.G; g.K = f.Cin / f.G; g.M = f.Cout / f.G; g.HW = f.HW;
+    g.Q = ceil_div(f.HW, 4);
+    p.mt = g.M <= 2 ? 2 : (g.M <= 4 ? 4 : 8);
+    g.mtiles = ceil_div(g.M, p.mt);
+    p.lds = (size_t)f.Cout * g.K * sizeof(float);
+    MSPL_REQUIRE(p.lds <= 48 * 1024, MSPL_ERR_UNSUPPORTED, "conv1x1(small-K): weight block %zu B exceeds LDS", p.lds);
+    const int64_t slabs = (int64_t)f.N * f.G * g.mtiles;
     MSPL_REQUIRE(slabs < 65535ll * 65535ll, MSPL_ERR_BAD_SHAPE, "conv1x1: grid too large");
     const int gy = slabs < 65535 ? (int)slabs : 65535;
-    dim3 grid((unsigned)ceil_div(g.Q, 256), (unsigned)gy, (unsigned)ceil_div64(slabs, gy)), blk(256);
-    if (mt == 2) hipLaunchKernelGGL(conv1x1_valu_kernel<2>, grid, blk, lds, s, x, w, g, e, out);
-    else if (mt == 4) hipLaunchKernelGGL(conv1x1_valu_kernel<4>, grid, blk, lds, s, x, w, g, e, out);
-    else hipLaunchKernelGGL(conv1x1_valu_kernel<8>, grid, blk, lds, s, x, w, g, e, out);
+    p.gx = (unsigned)ceil_div(g.Q, 256); p.gy = (unsigned)gy; p.gz = (unsigned)ceil_div64(slabs, gy);
+    return MSPL_OK;
+}
+
+static int launch_small(const float* x, const float* w, const PwPlan& p, const Epi& e, float* out, hipStream_t s) {
+    const dim3 grid(p.gx, p.gy, p.gz), blk(256);
+    if (p.mt == 2) hipLaunchKernelGGL(conv1x1_valu_kernel<2>, grid, blk, p.lds, s, x, w, p.sg, e, out);
+    else if (p.mt == 4) hipLaunchKernelGGL(conv1x1_valu_kernel<4>, grid, blk, p.lds, s, x, w, p.sg, e, out);
+    else hipLaunchKernelGGL(conv1x1_valu_kernel<8>, grid, blk, p.lds, s, x, w, p.sg, e, out);
     MSPL_CHECK_LAUNCH("conv1x1(small-K)");
     return MSPL_OK;
 }
 
-extern "C" int mspl_conv1x1_fwd(const float* x, const float* w, int32_t N, int32_t Cin, int32_t Cout,
-                                int32_t groups, int32_t HW, const mspl_epilogue_t* ep, float* out,
-                                void* stream) {
-    MSPL_REQUIRE(x && w && out, MSPL_ERR_NULL_POINTER, "conv1x1: null pointer");
+// The one place the form of a 1x1 launch is decided: mspl_conv1x1_fwd launches what this answers, mspl_conv1x1_fwd_plan reports it.
+// Host only, no device call, no state.  A refusal is the launcher's: its error code, with the error text set.
+static int pw_decide(const PwFacts& f, PwPlan& p) {
+    const int N = f.N, Cin = f.Cin, Cout = f.Cout, groups = f.G, HW = f.HW;
     MSPL_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && groups > 0 && HW > 0, MSPL_ERR_BAD_SHAPE,
                  "conv1x1: bad shape N=%d Cin=%d Cout=%d groups=%d HW=%d", N, Cin, Cout, groups, HW);
     MSPL_REQUIRE(Cin % groups == 0 && Cout % groups == 0, MSPL_ERR_BAD_SHAPE,
                  "conv1x1: channels (%d,%d) not divisible by groups %d", Cin, Cout, groups);
-    if (int rc = check_epi(ep, Cout, "conv1x1", true)) return rc;
-    const Epi e = make_epi(ep, Cout, HW);
-    hipStream_t s = (hipStream_t)stream;
-    PwGeom g;
-    memset(&g, 0, sizeof(g));
+    memset(&p, 0, sizeof(p));
+    PwGeom& g = p.g;
     g.N = N; g.Cin = Cin; g.Cout = Cout; g.G = groups; g.K = Cin / groups; g.M = Cout / groups; g.HW = HW;
-    if (launch_thin_try(x, w, N, Cin, Cout, groups, HW, e, out, s) == 0) {
-        MSPL_CHECK_LAUNCH("conv1x1(thin)");
+    if (plan_thin(f, p) == 0) {
+        p.form = MSPL_PW_FORM_THIN;
         return MSPL_OK;
     }
-    if ((g.K < 16 || (g.K & 1)) && (size_t)Cout * g.K * 4 <= 48 * 1024) return launch_small(x, w, N, Cin, Cout, groups, HW, e, out, s);
+    if ((g.K < 16 || (g.K & 1)) && (size_t)Cout * g.K * 4 <= 48 * 1024) {
+        p.form = MSPL_PW_FORM_SMALL_K;
+        return plan_small(f, p);
+    }
     MSPL_REQUIRE((g.K & 1) == 0, MSPL_ERR_UNSUPPORTED, "conv1x1: odd K=%d per group with %d output channels is not supported", g.K, Cout);
 
-    if (conv1x1_splitk_try(x, w, N, Cin, Cout, groups, HW, e, out, s) == 0) {      // few output channels per group: split-K form
-        MSPL_CHECK_LAUNCH("conv1x1(split-K)");
+    if (conv1x1_splitk_plan(N, g.M, g.K, groups, HW, f.lean, &p.sk) == 0) {       // few output channels per group: split-K form
+        p.form = MSPL_PW_FORM_SPLIT_K;
+        p.nsub = p.sk.nsub;
+        p.gx = (unsigned)p.sk.blocks; p.gy = p.gz = 1;
         return MSPL_OK;
     }
     const int K32 = (g.K + 31) & ~31;
     g.KS = K32 | 1;
-    g.vecw = ((g.K & 3) == 0) && ((((uintptr_t)w) & 15) == 0);
+    g.vecw = ((g.K & 3) == 0) && f.aw >= 16;
     static const int dbg_areg = MSPL_TUNE_INT("MSPL_PW_AREG", 1);
     const int ng8 = g.K >> 3;
     const bool ng_ok = ng8 == 2 || ng8 == 3 || ng8 == 4 || ng8 == 6 || ng8 == 8 || ng8 == 12 || ng8 == 16;
@@ -1051,15 +1107,18 @@ extern "C" int mspl_conv1x1_fwd(const float* x, const float* w, int32_t N, int32
     const bool areg_shape = dbg_areg == 2 || (g.K <= 32 && (int64_t)N * HW >= 100000);
     static const int dbg_pipe = MSPL_TUNE_INT("MSPL_PW_PIPE", 1);
     const bool pipe_shape = true;      // measured faster than the LDS-ring and register-weights forms on every eligible shape
-    if (dbg_pipe && pipe_shape && (g.K & 7) == 0 && (ng_ok || ng_big) && g.vecw &&
-        (size_t)N * Cin * HW * sizeof(float) < (1ull << 32) && (size_t)N * e.ctot * HW * sizeof(float) < (1ull << 32))
-        return launch_pipe(x, w, g, e, ep, out, s);
-    if (dbg_areg && areg_shape && (g.K & 7) == 0 && ng_ok && g.vecw &&
-        (size_t)N * Cin * HW * sizeof(float) < (1ull << 32) && (size_t)N * e.ctot * HW * sizeof(float) < (1ull << 32))
-        return launch_areg(x, w, g, e, ep, out, s);
+    const bool fits32 = (size_t)N * Cin * HW * sizeof(float) < (1ull << 32) && (size_t)N * f.ctot * HW * sizeof(float) < (1ull << 32);
+    if (dbg_pipe && pipe_shape && (g.K & 7) == 0 && (ng_ok || ng_big) && g.vecw && fits32) {
+        p.form = MSPL_PW_FORM_TILE_PIPELINED;
+        return plan_pipe(f, p);
+    }
+    if (dbg_areg && areg_shape && (g.K & 7) == 0 && ng_ok && g.vecw && fits32) {
+        p.form = MSPL_PW_FORM_REGISTER_WEIGHTS;
+        return plan_areg(f, p);
+    }
+    p.form = MSPL_PW_FORM_LDS_RING;
     const int rowf = ROWC;
-    MSPL_REQUIRE((size_t)N * Cin * HW * sizeof(float) < (1ull << 32) && (size_t)N * e.ctot * HW * sizeof(float) < (1ull << 32),
-                 MSPL_ERR_UNSUPPORTED, "conv1x1: tensor exceeds the 32-bit byte offsets of the matrix-core kernel");
+    MSPL_REQUIRE(fits32, MSPL_ERR_UNSUPPORTED, "conv1x1: tensor exceeds the 32-bit byte offsets of the matrix-core kernel");
     const size_t lds_cap = 96 * 1024;       // hard cap (of the 160 KiB per CU)
     static const int dbg_lds = MSPL_TUNE_INT("MSPL_PW_LDS", 0);
     const size_t lds_want = dbg_lds ? (size_t)dbg_lds * 1024 : 40 * 1024;      // preferred: several workgroups per CU
@@ -1073,10 +1132,45 @@ extern "C" int mspl_conv1x1_fwd(const float* x, const float* w, int32_t N, int32
     g.mc_total = mb / 32;
     g.WM = g.mc_total >= 3 ? 4 : g.mc_total;     // one 32-row chunk per wave; chunks share B loads through L1
     const int wp = 4 / g.WM;
-    const size_t lds = (size_t)g.MB * (g.KS + rowf) * sizeof(float);
+    p.lds = (size_t)g.MB * (g.KS + rowf) * sizeof(float);
+    // pixels per lane: the widest vector the shape/alignment allows that still yields enough waves to fill
+    // 256 CUs x 4 SIMDs (small feature maps prefer narrower tiles over idle CUs)
+    auto ok = [&](int ns) { return pw_vec_ok(f, ns); };
+    auto waves_of = [&](int ns) { return (int64_t)groups * g.mblocks * g.mc_total * ceil_div64((int64_t)N * HW, 32 * ns); };
+    int nsub = 1;
+    if (ok(4) && waves_of(4) >= 2048) nsub = 4;
+    else if (ok(2) && waves_of(2) >= 2048) nsub = 2;
+    else if (ok(2) && !ok(1)) nsub = 2;
+    static const int dbg_nsub = MSPL_TUNE_INT("MSPL_PW_NSUB", 0);   // tuning override
+    static const int dbg_tpw = MSPL_TUNE_INT("MSPL_PW_TPW", 0);
+    if (dbg_nsub && ok(dbg_nsub)) nsub = dbg_nsub;
+    p.nsub = nsub;
+    g.ptiles = (int)ceil_div64((int64_t)N * HW, 32 * nsub);
+    const int64_t wave_tiles = (int64_t)groups * g.mblocks * g.ptiles;
+    int tpw = 1;
+    while (tpw < 4 && wave_tiles / (wp * tpw * 2) >= 2048) tpw *= 2;
+    if (dbg_tpw) tpw = dbg_tpw;
+    g.TPW = tpw;
+    g.pgroups = ceil_div(g.ptiles, wp * tpw);
+    const int64_t blocks = (int64_t)groups * g.mblocks * g.pgroups;
+    MSPL_REQUIRE(blocks < (1ll << 31), MSPL_ERR_BAD_SHAPE, "conv1x1: grid too large");
+    p.gx = (unsigned)blocks; p.gy = p.gz = 1;
+    // ring depth = B groups (8 k-values each) in flight per wave (deeper rings measured slower: they cost occupancy)
+    p.ring = 4;
+    static const int dbg_ring = MSPL_TUNE_INT("MSPL_PW_RING", 0);
+    if (nsub < 4 && (dbg_ring == 4 || dbg_ring == 8 || dbg_ring == 16)) p.ring = dbg_ring;
+    return MSPL_OK;
+}
+
+// Launch of the LDS-ring kernel as planned.
+static int launch_ring(const float* x, const float* w, const PwPlan& p, const Epi& e, float* out, hipStream_t s) {
+    PwGeom g = p.g;
+    const int nsub = p.nsub, ring = p.ring;
+    const size_t lds = p.lds;
+    const int64_t blocks = p.gx;
     static std::once_flag attr_once;   // dynamic LDS above 64 KiB needs the opt-in (once per process, thread-safe)
     {
-        constexpr int cap = 96 * 1024;            // = lds_cap
+        constexpr int cap = 96 * 1024;            // = pw_decide's lds_cap
         std::call_once(attr_once, [] {
             (void)hipFuncSetAttribute((const void*)conv1x1_mfma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
             (void)hipFuncSetAttribute((const void*)conv1x1_mfma_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
@@ -1088,39 +1182,11 @@ extern "C" int mspl_conv1x1_fwd(const float* x, const float* w, int32_t N, int32
             (void)hipGetLastError();
         });
     }
-    // pixels per lane: the widest vector the shape/alignment allows that still yields enough waves to fill
-    // 256 CUs x 4 SIMDs (small feature maps prefer narrower tiles over idle CUs)
-    auto al = [](const void* p, int a) { return p == nullptr || (((uintptr_t)p) & (a - 1)) == 0; };
-    auto ok = [&](int ns) {
-        const int a = ns * 4;
-        return HW % ns == 0 && al(x, a) && al(out, a) && (!ep || (al(ep->pre_add, a) && al(ep->residual, a) && al(ep->reinf_r, a)));
-    };
-    auto waves_of = [&](int ns) { return (int64_t)groups * g.mblocks * g.mc_total * ceil_div64((int64_t)N * HW, 32 * ns); };
-    int nsub = 1;
-    if (ok(4) && waves_of(4) >= 2048) nsub = 4;
-    else if (ok(2) && waves_of(2) >= 2048) nsub = 2;
-    else if (ok(2) && !ok(1)) nsub = 2;
-    static const int dbg_nsub = MSPL_TUNE_INT("MSPL_PW_NSUB", 0);   // tuning override
-    static const int dbg_tpw = MSPL_TUNE_INT("MSPL_PW_TPW", 0);
-    if (dbg_nsub && ok(dbg_nsub)) nsub = dbg_nsub;
-    g.ptiles = (int)ceil_div64((int64_t)N * HW, 32 * nsub);
-    const int64_t wave_tiles = (int64_t)groups * g.mblocks * g.ptiles;
-    int tpw = 1;
-    while (tpw < 4 && wave_tiles / (wp * tpw * 2) >= 2048) tpw *= 2;
-    if (dbg_tpw) tpw = dbg_tpw;
-    g.TPW = tpw;
-    g.pgroups = ceil_div(g.ptiles, wp * tpw);
-    const int64_t blocks = (int64_t)groups * g.mblocks * g.pgroups;
-    MSPL_REQUIRE(blocks < (1ll << 31), MSPL_ERR_BAD_SHAPE, "conv1x1: grid too large");
     static unsigned long long* stamp_buf = nullptr;
     static const int dbg_stamp = MSPL_STAMP_ENV("MSPL_PW_STAMP");
     if (dbg_stamp && !stamp_buf) (void)hipMalloc(&stamp_buf, (size_t)5 * 65536 * sizeof(unsigned long long));
     g.stamps = (dbg_stamp && blocks <= 65536) ? stamp_buf : nullptr;
-    dim3 grid((unsigned)blocks), blk(256);
-    // ring depth = B groups (8 k-values each) in flight per wave (deeper rings measured slower: they cost occupancy)
-    int ring = 4;
-    static const int dbg_ring = MSPL_TUNE_INT("MSPL_PW_RING", 0);
-    if (nsub < 4 && (dbg_ring == 4 || dbg_ring == 8 || dbg_ring == 16)) ring = dbg_ring;
+    dim3 grid(p.gx), blk(256);
 #define MSPL_PW(NS, RG) hipLaunchKernelGGL((conv1x1_mfma_kernel<NS, RG>), grid, blk, lds, s, x, w, g, e, out)
     if (nsub == 4) MSPL_PW(4, 4);
     else if (nsub == 2) { if (ring == 16) MSPL_PW(2, 16); else if (ring == 8) MSPL_PW(2, 8); else MSPL_PW(2, 4); }
@@ -1151,5 +1217,80 @@ extern "C" int mspl_conv1x1_fwd(const float* x, const float* w, int32_t N, int32
                 (unsigned)hwid[0], (unsigned)(hwid[0] >> 32));
     }
     MSPL_CHECK_LAUNCH("conv1x1");
+    return MSPL_OK;
+}
+
+extern "C" int mspl_conv1x1_fwd(const float* x, const float* w, int32_t N, int32_t Cin, int32_t Cout,
+                                int32_t groups, int32_t HW, const mspl_epilogue_t* ep, float* out,
+                                void* stream) {
+    MSPL_REQUIRE(x && w && out, MSPL_ERR_NULL_POINTER, "conv1x1: null pointer");
+    MSPL_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && groups > 0 && HW > 0, MSPL_ERR_BAD_SHAPE,
+                 "conv1x1: bad shape N=%d Cin=%d Cout=%d groups=%d HW=%d", N, Cin, Cout, groups, HW);
+    MSPL_REQUIRE(Cin % groups == 0 && Cout % groups == 0, MSPL_ERR_BAD_SHAPE,
+                 "conv1x1: channels (%d,%d) not divisible by groups %d", Cin, Cout, groups);
+    if (int rc = check_epi(ep, Cout, "conv1x1", true)) return rc;
+    const Epi e = make_epi(ep, Cout, HW);
+    hipStream_t s = (hipStream_t)stream;
+    PwFacts f;
+    f.N = N; f.Cin = Cin; f.Cout = Cout; f.G = groups; f.HW = HW; f.ctot = e.ctot;
+    f.lean = !(e.pre_add || e.residual || e.reinf_r || e.gate);
+    f.ax = pw_align(x); f.aw = pw_align(w); f.aout = pw_align(out);
+    f.aop = std::min(pw_align(e.pre_add), std::min(pw_align(e.residual), pw_align(e.reinf_r)));
+    f.aside = std::min(pw_align(e.raw), pw_align(e.gate));
+    PwPlan p;
+    if (int rc = pw_decide(f, p)) return rc;
+    switch (p.form) {
+        case MSPL_PW_FORM_THIN:
+            launch_thin(x, w, p, e, out, s);
+            MSPL_CHECK_LAUNCH("conv1x1(thin)");
+            return MSPL_OK;
+        case MSPL_PW_FORM_SMALL_K: return launch_small(x, w, p, e, out, s);
+        case MSPL_PW_FORM_SPLIT_K:
+            conv1x1_splitk_launch(x, w, N, p.g.M, p.g.K, groups, HW, p.sk, e, out, s);
+            MSPL_CHECK_LAUNCH("conv1x1(split-K)");
+            return MSPL_OK;
+        case MSPL_PW_FORM_TILE_PIPELINED: return launch_pipe(x, w, p, e, out, s);
+        case MSPL_PW_FORM_REGISTER_WEIGHTS: return launch_areg(x, w, p, e, out, s);
+        default: return launch_ring(x, w, p, e, out, s);
+    }
+}
+
+extern "C" int mspl_conv1x1_fwd_plan(int32_t N, int32_t Cin, int32_t Cout, int32_t groups, int32_t HW, int32_t out_ctot,
+                                     uint32_t terms, int32_t x_align, int32_t w_align, int32_t out_align, int32_t operand_align,
+                                     int32_t side_align, int32_t* out) {
+    MSPL_REQUIRE(out, MSPL_ERR_NULL_POINTER, "conv1x1_fwd_plan: null out");
+    auto pow2 = [](int a) { return a == 1 || a == 2 || a == 4 || a == 8 || a == 16; };
+    MSPL_REQUIRE(pow2(x_align) && pow2(w_align) && pow2(out_align) && pow2(operand_align) && pow2(side_align), MSPL_ERR_BAD_SHAPE,
+                 "conv1x1_fwd_plan: alignments (%d,%d,%d,%d,%d) must be 1, 2, 4, 8 or 16", x_align, w_align, out_align, operand_align,
+                 side_align);
+    MSPL_REQUIRE(out_ctot == 0 || out_ctot >= Cout, MSPL_ERR_BAD_SHAPE, "conv1x1_fwd_plan: destination with %d channels for %d outputs",
+                 out_ctot, Cout);
+    PwFacts f;
+    f.N = N; f.Cin = Cin; f.Cout = Cout; f.G = groups; f.HW = HW; f.ctot = out_ctot > 0 ? out_ctot : Cout;
+    f.lean = !(terms & (MSPL_PW_TERM_PRE_ADD | MSPL_PW_TERM_RESIDUAL | MSPL_PW_TERM_REINF | MSPL_PW_TERM_GATE));
+    f.ax = x_align; f.aw = w_align; f.aout = out_align; f.aop = operand_align; f.aside = side_align;
+    for (int i = 0; i < MSPL_PW_PLAN_LEN; ++i) out[i] = 0;
+    PwPlan p;
+    if (int rc = pw_decide(f, p)) return rc;
+    out[MSPL_PW_PLAN_FORM] = p.form;
+    out[MSPL_PW_PLAN_LDS_BYTES] = (int32_t)p.lds;
+    out[MSPL_PW_PLAN_GRID_X] = (int32_t)p.gx;  out[MSPL_PW_PLAN_GRID_Y] = (int32_t)p.gy;  out[MSPL_PW_PLAN_GRID_Z] = (int32_t)p.gz;
+    switch (p.form) {
+        case MSPL_PW_FORM_THIN:
+        case MSPL_PW_FORM_SMALL_K:
+            out[MSPL_PW_PLAN_MT] = p.mt;  out[MSPL_PW_PLAN_MTILES] = p.sg.mtiles;
+            break;
+        case MSPL_PW_FORM_SPLIT_K:
+            out[MSPL_PW_PLAN_NSUB] = p.sk.nsub;  out[MSPL_PW_PLAN_CH] = p.sk.ch;  out[MSPL_PW_PLAN_KS] = p.sk.ks;
+            out[MSPL_PW_PLAN_TILES] = p.sk.tiles;
+            break;
+        default:
+            out[MSPL_PW_PLAN_NSUB] = p.nsub;  out[MSPL_PW_PLAN_MB] = p.g.MB;  out[MSPL_PW_PLAN_WM] = p.g.WM;
+            out[MSPL_PW_PLAN_TPW] = p.g.TPW;  out[MSPL_PW_PLAN_KS] = p.g.KS;  out[MSPL_PW_PLAN_VECW] = p.g.vecw;
+            if (p.form == MSPL_PW_FORM_LDS_RING) out[MSPL_PW_PLAN_RING] = p.ring;
+            else out[MSPL_PW_PLAN_NG] = p.ng;
+            if (p.form == MSPL_PW_FORM_TILE_PIPELINED) out[MSPL_PW_PLAN_AR] = p.g.AR;
+            break;
+    }
     return MSPL_OK;
 }

@@ -8,14 +8,14 @@
 //   lane (r = lane & 31, h = lane >> 5):  A element = w[grp*M + r][k + h],  B element = x[grp*K + k + h][pixel r (+32 per sub-tile)]
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "conv1x1_plan.hpp"
 
 namespace mspl {
 
 typedef float f32x16s __attribute__((ext_vector_type(16)));
 
 struct SkGeom {
-    int N, G, M, K, HW;      // images, groups, cout_g (<= 32), cin_g (% 8 == 0), pixels per plane
+    int N, G, M, K, HW;      // images, groups, cout_g (<= 32), cin_g (% 64 == 0), pixels per plane
     int tiles;               // pixel tiles per image (32 * NSUB pixels each)
     int KS;                  // k per wave = K / 4
 };
@@ -84,35 +84,42 @@ __global__ __launch_bounds__(256) void conv1x1_splitk_kernel(const float* __rest
     }
 }
 
-// Returns 1 when the shape / epilogue is not this kernel's (the caller continues with the tile-pipelined kernel).
-int conv1x1_splitk_try(const float* x, const float* w, int N, int Cin, int Cout, int groups, int HW, const Epi& e, float* out,
-                       hipStream_t s) {
+// Returns 1 when the shape / epilogue is not this kernel's (the caller continues with the tile-pipelined kernel).  Host only.
+int conv1x1_splitk_plan(int N, int M, int K, int groups, int HW, bool lean, SkPlan* p) {
     static const int enabled = MSPL_TUNE_INT("MSPL_PW_SPLITK", 1);
-    const int M = Cout / groups, K = Cin / groups;
-    if (!enabled || M > 32 || K < 64 || (K & 31) != 0) return 1;          // K/4 per wave in chunks of 8 or 16 MFMA steps
+    // K/4 per wave, walked in chunks of 2*CH k with CH = 8 or 16 and no tail: K/4 must be a multiple of 16, K of 64.  (K = 96, 160,
+    // 224, ... have K/4 = 24, 40, 56: a chunk of 16 would run 8 k past the wave's slice -- into the next wave's, the next weight
+    // row and the next image.  They go to the tile-pipelined / LDS-ring forms.)
+    if (!enabled || M > 32 || K < 64 || (K & 63) != 0) return 1;
     // measured (tools/bench_ops.py conv1x1): wins for the ungrouped deep-and-narrow projections of the pyramid (512->16: 22.1 ->
     // 12.6 us, 64->16: 8.2 -> 6.8 us); loses to the tile-pipelined kernel on the grouped EESP projections (512->128 g4: 11.7 vs 14.3 us)
     if (groups != 1 || K < 4 * M) return 1;
-    if (e.pre_add || e.residual || e.reinf_r || e.gate) return 1;
+    if (!lean) return 1;
     // worth it where the tile-pipelined kernel starves: fewer than ~2 waves per SIMD there
     const int64_t pipe_waves = (int64_t)N * groups * ceil_div(HW, 32);
     if (pipe_waves > 6000) return 1;
+    p->ks = K / 4;
+    p->nsub = (int64_t)N * groups * ceil_div(HW, 64) >= 1024 ? 2 : 1;
+    p->tiles = ceil_div(HW, 32 * p->nsub);
+    p->blocks = (int64_t)N * groups * p->tiles;
+    if (p->blocks >= (1ll << 31)) return 1;
+    p->ch = (p->ks % 32) == 0 ? 16 : 8;                                   // 16 steps = 32 k per chunk when the slice allows
+    if (p->ks % (2 * p->ch) != 0) return 1;                               // the kernel's k-loop has no tail
+    return 0;
+}
+
+void conv1x1_splitk_launch(const float* x, const float* w, int N, int M, int K, int groups, int HW, const SkPlan& p, const Epi& e,
+                           float* out, hipStream_t s) {
     SkGeom g;
-    g.N = N; g.G = groups; g.M = M; g.K = K; g.HW = HW; g.KS = K / 4;
-    const int nsub = (int64_t)N * groups * ceil_div(HW, 64) >= 1024 ? 2 : 1;
-    g.tiles = ceil_div(HW, 32 * nsub);
-    const int64_t blocks = (int64_t)N * groups * g.tiles;
-    if (blocks >= (1ll << 31)) return 1;
-    const dim3 grid((unsigned)blocks), blk(256);
-    const bool ch16 = (g.KS % 32) == 0;                                   // 16 steps = 32 k per chunk when the slice allows
-    if (nsub == 2) {
-        if (ch16) hipLaunchKernelGGL((conv1x1_splitk_kernel<2, 16>), grid, blk, 0, s, x, w, g, e, out);
+    g.N = N; g.G = groups; g.M = M; g.K = K; g.HW = HW; g.KS = p.ks; g.tiles = p.tiles;
+    const dim3 grid((unsigned)p.blocks), blk(256);
+    if (p.nsub == 2) {
+        if (p.ch == 16) hipLaunchKernelGGL((conv1x1_splitk_kernel<2, 16>), grid, blk, 0, s, x, w, g, e, out);
         else hipLaunchKernelGGL((conv1x1_splitk_kernel<2, 8>), grid, blk, 0, s, x, w, g, e, out);
     } else {
-        if (ch16) hipLaunchKernelGGL((conv1x1_splitk_kernel<1, 16>), grid, blk, 0, s, x, w, g, e, out);
+        if (p.ch == 16) hipLaunchKernelGGL((conv1x1_splitk_kernel<1, 16>), grid, blk, 0, s, x, w, g, e, out);
         else hipLaunchKernelGGL((conv1x1_splitk_kernel<1, 8>), grid, blk, 0, s, x, w, g, e, out);
     }
-    return 0;
 }
 
 }  // namespace mspl

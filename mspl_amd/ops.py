@@ -236,6 +236,32 @@ def conv1x1(x, w, groups=1, ep=None, out=None):
     return dst
 
 
+CONV1X1_FORMS = {nat.PW_FORM_THIN: 'thin', nat.PW_FORM_SMALL_K: 'small_k', nat.PW_FORM_SPLIT_K: 'split_k',
+                 nat.PW_FORM_TILE_PIPELINED: 'pipe', nat.PW_FORM_REGISTER_WEIGHTS: 'areg', nat.PW_FORM_LDS_RING: 'ring'}
+CONV1X1_TERMS = {'scale': nat.PW_TERM_SCALE, 'shift': nat.PW_TERM_SHIFT, 'alpha': nat.PW_TERM_ALPHA, 'pre_add': nat.PW_TERM_PRE_ADD,
+                 'residual': nat.PW_TERM_RESIDUAL, 'reinf': nat.PW_TERM_REINF, 'gate': nat.PW_TERM_GATE, 'raw_out': nat.PW_TERM_RAW_OUT}
+_PW_PLAN_FIELDS = ('MT', 'MTILES', 'NSUB', 'CH', 'KS', 'TILES', 'NG', 'MB', 'AR', 'WM', 'TPW', 'RING', 'VECW', 'LDS_BYTES', 'GRID_X',
+                   'GRID_Y', 'GRID_Z')
+
+
+def conv1x1_plan(shape, terms=(), ctot=0, x_align=16, w_align=16, out_align=16, operand_align=16, side_align=16):
+    """The kernel form conv1x1 takes (mspl_conv1x1_fwd_plan, the launcher's own host function; no device call).
+    shape: (N, Cin, Cout, groups, HW); terms: names of the epilogue operands present (CONV1X1_TERMS); ctot: channels of the
+    destination (0: Cout); *_align: the power of two (<= 16) dividing the address of x / w / out, the per-pixel operands
+    (pre_add, residual, reinf_r) and raw_out / gate.  -> dict form ('thin' / 'small_k' / 'split_k' / 'pipe' / 'areg' / 'ring') and
+    the integers mt / mtiles / nsub / ch / ks / tiles / ng / mb / ar / wm / tpw / ring / vecw / lds_bytes / grid_x / grid_y / grid_z,
+    0 where they do not apply to the form.  A shape the launcher refuses raises what the launcher raises."""
+    out = (ctypes.c_int32 * nat.PW_PLAN_LEN)()
+    mask = 0
+    for t in terms:
+        mask |= CONV1X1_TERMS[t]
+    check(lib.mspl_conv1x1_fwd_plan(*[int(v) for v in shape], int(ctot), mask, int(x_align), int(w_align), int(out_align),
+                                    int(operand_align), int(side_align), out))
+    plan = {n.lower(): int(out[getattr(nat, 'PW_PLAN_' + n)]) for n in _PW_PLAN_FIELDS}
+    plan['form'] = CONV1X1_FORMS[int(out[nat.PW_PLAN_FORM])]
+    return plan
+
+
 def conv3x3(x, w, groups=1, stride=1, shuffle_groups=0, ep=None, out=None):
     x, w = _f32(x, 'x'), _f32(w, 'w')
     N, Cin, H, W = x.shape

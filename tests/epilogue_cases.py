@@ -60,11 +60,12 @@ OPS = {
     'conv1x1': dict(
         entry='mspl_conv1x1_fwd', accepts=EVERYTHING, refuses=frozenset(),
         termsets=(),             # operand terms: tests/test_gpu_kernels.py::test_conv1x1_epilogues; here raw_out and the split-K fall-back
-        # (N, Cin, Cout, G, H, W)
-        cases=[Case((2, 32, 24, 4, 16, 30), 'small-K vector-unit form (K = 8 per group)', 'conv1x1.hip:1034'),
-               Case((2, 512, 128, 4, 18, 30), 'matrix cores, tile-pipelined (grouped: not split-K)', 'conv1x1.hip:1054'),
-               Case((2, 128, 20, 1, 7, 11), 'split-K', 'conv1x1_splitk.hip:95'),
-               Case((12, 32, 16, 1, 144, 240), 'streaming vector-unit form', 'conv1x1.hip:839')]),
+        # (N, Cin, Cout, G, H, W); the form is the library's own answer (ops.conv1x1_plan; CONV1X1_PLAN_FORMS below is checked against
+        # it by tests/test_conv1x1_cases.py, and tests/conv1x1_cases.py holds the exact-data cases of every form's seams)
+        cases=[Case((2, 32, 24, 4, 16, 30), 'small-K vector-unit form (K = 8 per group)', 'conv1x1.hip:pw_decide'),
+               Case((2, 512, 128, 4, 18, 30), 'matrix cores, tile-pipelined (grouped: not split-K)', 'conv1x1.hip:pw_decide'),
+               Case((2, 128, 20, 1, 7, 11), 'split-K', 'conv1x1_splitk.hip:conv1x1_splitk_plan'),
+               Case((12, 32, 16, 1, 144, 240), 'streaming vector-unit form', 'conv1x1.hip:plan_thin')]),
     'bilinear': dict(
         entry='mspl_bilinear_fwd', accepts=ALL | {'slice'}, refuses=frozenset({'raw_out'}),
         # ((N, C, Hi, Wi), (Ho, Wo), align_corners)
@@ -155,6 +156,8 @@ RAW_OPS = ('conv3x3', 'conv1x1', 'eesp_dw_hff', 'pyrpool_fused_train')
 # (op, case index, the term set of the lean form): a neutral further operand moves the call off the form
 FALLBACKS = [('conv1x1', 2, AFFINE), ('pyrpool_fused', 0, AFFINE), ('pyrpool_fused', 2, AFFINE),
              ('avgpool3x3s2_psum', 2, DOWN), ('avgpool3x3s2_psum', 3, DOWN)]
+# what mspl_conv1x1_fwd_plan answers for the conv1x1 cases above, in their order (ops.CONV1X1_FORMS names)
+CONV1X1_PLAN_FORMS = ('small_k', 'pipe', 'split_k', 'thin')
 PYR_SCALES = (2.0, 1.5, 1.0, 0.5, 0.1)
 
 

@@ -201,9 +201,11 @@ def test_eesp_dw_unsupported_dilation_raises():
     (2, 32, 24, 4, 16, 30), (1, 512, 512, 4, 16, 30), (2, 256, 64, 4, 9, 13), (1, 512, 16, 1, 16, 30),
     (2, 96, 96, 4, 8, 12), (1, 16, 13, 1, 17, 23), (1, 48, 16, 1, 20, 20), (2, 16, 4, 4, 10, 10),
     (1, 128, 512, 4, 6, 6), (1, 160, 640, 4, 5, 9), (1, 3, 128, 1, 12, 16), (1, 512, 64, 1, 4, 8),
+    # (the form a shape takes is what ops.conv1x1_plan answers; tests/conv1x1_cases.py pins form and variant per seam, on exact data)
     # many pixel tiles: several tiles per wave (the ring runs across tiles), 48 rows in a 64-row weight tile, odd pixel count
     (1, 32, 16, 1, 288, 720), (1, 64, 96, 2, 160, 320), (3, 24, 8, 1, 191, 201),
-    # few output channels per group on small maps: the split-K form (EESP reduce projections at levels 3 / 4, pyramid projections)
+    # few output channels per group on small maps: EESP reduce projections at levels 3 / 4 (grouped: tile-pipelined) and a pyramid
+    # projection (ungrouped, K % 64 == 0: the split-K form)
     (2, 512, 128, 4, 18, 30), (3, 256, 64, 4, 36, 60), (2, 128, 20, 1, 7, 11),
     # thin projections on large maps: the streaming vector-unit form (<= 16 output channels per group, >= 400 workgroups)
     (12, 32, 16, 1, 144, 240), (8, 32, 24, 4, 144, 240), (12, 16, 13, 1, 144, 240)])

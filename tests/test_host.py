@@ -132,6 +132,12 @@ def test_binding_spot_checks_against_the_real_header():
     assert sig['mspl_last_error'] == [c.c_char_p, c.c_size_t] and res['mspl_last_error'] is c.c_size_t
     assert sig['mspl_version'] == [] and res['mspl_version'] is c.c_char_p
     assert sig['mspl_conv1x1_fwd'] == [p, p] + [i32] * 5 + [_native._EP, p, p] and res['mspl_conv1x1_fwd'] is c.c_int
+    assert sig['mspl_conv1x1_fwd_plan'] == [i32] * 6 + [c.c_uint32] + [i32] * 5 + [p] and res['mspl_conv1x1_fwd_plan'] is c.c_int
+    assert [_native.PW_FORM_THIN, _native.PW_FORM_SMALL_K, _native.PW_FORM_SPLIT_K, _native.PW_FORM_TILE_PIPELINED,
+            _native.PW_FORM_REGISTER_WEIGHTS, _native.PW_FORM_LDS_RING] == list(range(1, 7))
+    assert [getattr(_native, 'PW_TERM_' + t) for t in ('SCALE', 'SHIFT', 'ALPHA', 'PRE_ADD', 'RESIDUAL', 'REINF', 'GATE', 'RAW_OUT')] == \
+        [1 << i for i in range(8)]
+    assert _native.PW_PLAN_LEN == 18 and _native.PW_PLAN_FORM == 0
     assert _native._EP is c.POINTER(_native.Epilogue)
     assert res['mspl_bn_fused_workspace_bytes'] is c.c_int64 and res['mspl_nid_workspace_floats'] is c.c_int64      # size queries
     assert (_native.FILTER_LANCZOS, _native.FILTER_BILINEAR, _native.ERR_UNSUPPORTED) == (1, 2, -2)
