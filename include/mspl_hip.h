@@ -918,6 +918,49 @@ int mspl_nid_hist_fwd(const float* camera, const float* label, int32_t B, int32_
 int mspl_nid_hist_bwd(const float* camera, const float* label, int32_t B, int32_t C, int32_t H, int32_t W, int32_t K,
                       float bw_camera, float bw_label, const float* gjoint, const float* gpl, float* glabel, void* stream);
 
+/* NIDLoss at head resolution: NIDLoss(camera, F.interpolate(main_lo, (H,W), mode='bilinear', align_corners=True)), that is
+ * loss_fns/segmentation_loss.py:54-144 on the main head of model/segmentation/espdnet_ue.py:301, from the decoder's low-resolution
+ * output main_lo (B,C,Hm,Wm); no (B,C,H,W) tensor is written or read in either direction.  A pixel's up-sampled logits are
+ * computed with the operations and in the order of mspl_bilinear_fwd (align_corners), its soft-arg-max and sigmoids by the device
+ * code of mspl_nid_hist_fwd, so per-pixel values are the same floats as in the three-step form mspl_bilinear_fwd ->
+ * mspl_nid_hist_fwd / mspl_nid_hist_bwd -> mspl_bilinear_bwd; only the order of the sums over positions differs.
+ *
+ * mspl_nid_heads_fwd (replaces :65-96 and :124-141 behind the interpolation): out = joint (K,Cl) | p_c (K) | p_l (Cl), Cl = min(C,K),
+ *     divided by B*H*W: the layout of mspl_nid_hist_fwd.  Deterministic (per-workgroup partials, fixed-order sum in double).  ws:
+ *     mspl_nid_heads_workspace_floats(C,H,W,K) floats; besides the partials it receives the per-position camera columns P_c (K,H*W),
+ *     which depend on the batch alone and which mspl_nid_heads_bwd reads instead of recomputing B * 2K sigmoids per position.
+ * mspl_nid_finalize (replaces :98-118): from `out`, loss2[0] = (1 - I/H - 0.95) * 20 with the normalisations p / p.sum() and eps =
+ *     1e-7, over the first min(label_bin, Cl) label bins (label_bin <= C; the reference never fills a bin beyond Cl), and the closed-form
+ *     gjoint (K,Cl) = d loss2 / d joint, gpl (Cl) = d loss2 / d p_l, both divided by norm = B*H*W as mspl_nid_hist_bwd and
+ *     mspl_nid_heads_bwd expect them (entries of bins that do not enter the loss are 0).  One workgroup, double precision inside.
+ * mspl_nid_heads_bwd (the backward of :65-96, :124-141 and of the interpolation): gmain_lo (B,C,Hm,Wm) += gscale[0] * d loss2 / d
+ *     main_lo.  ACCUMULATED into with float atomics (the caller zeroes it): a band's gradient is summed in an LDS accumulator of its
+ *     head patch, and patches of neighbouring bands overlap, so bits may differ from run to run.  Pixels whose d loss2 / d lab is
+ *     exactly zero in fp32 (all but near-ties of adjacent classes at beta = 500, bw_label = 1e-3) are skipped.  ws: as left by
+ *     mspl_nid_heads_fwd on the same camera and shape.  gscale: device scalar, the upstream gradient; NULL = 1.
+ * mspl_nid_heads_plan: what the launchers decide for a shape, from the host function they call themselves (no device call, no
+ *     state); out: MSPL_NH_PLAN_LEN integers.  K or C above 32, a head larger than the label map or columns and patches beyond the
+ *     LDS budget: MSPL_ERR_UNSUPPORTED from the plan and from both launchers, which then launch nothing and leave their outputs
+ *     untouched (callers take the three-step form). */
+#define MSPL_NH_PLAN_BAND_ROWS 0        /* label-map rows x columns of one workgroup's band of positions */
+#define MSPL_NH_PLAN_BAND_COLS 1
+#define MSPL_NH_PLAN_PATCH_ROWS 2       /* LDS capacity of the head patch a band interpolates from (the row stride is PATCH_COLS) */
+#define MSPL_NH_PLAN_PATCH_COLS 3
+#define MSPL_NH_PLAN_LDS_FWD 4          /* dynamic LDS bytes of the forward / backward launch */
+#define MSPL_NH_PLAN_LDS_BWD 5
+#define MSPL_NH_PLAN_BANDS 6            /* workgroups of either launch */
+#define MSPL_NH_PLAN_FAN 7              /* most label positions one head pixel is a source of */
+#define MSPL_NH_PLAN_LEN 8
+int mspl_nid_heads_plan(int32_t B, int32_t C, int32_t Hm, int32_t Wm, int32_t H, int32_t W, int32_t K, int32_t* out);
+int64_t mspl_nid_heads_workspace_floats(int32_t C, int32_t H, int32_t W, int32_t K);
+int mspl_nid_heads_fwd(const float* camera, const float* main_lo, int32_t B, int32_t C, int32_t Hm, int32_t Wm, int32_t H, int32_t W,
+                       int32_t K, float bw_camera, float bw_label, float* ws, float* out, void* stream);
+int mspl_nid_finalize(const float* out, int32_t K, int32_t C, int32_t label_bin, double norm, float* loss2, float* gjoint,
+                      float* gpl, void* stream);
+int mspl_nid_heads_bwd(const float* main_lo, int32_t B, int32_t C, int32_t Hm, int32_t Wm, int32_t H, int32_t W, int32_t K,
+                       float bw_label, const float* ws, const float* gjoint, const float* gpl, const float* gscale, float* gmain_lo,
+                       void* stream);
+
 /* Backward of mspl_eesp_dw_hff_fwd (K2) in two launches.  gs: the suffix-summed output gradient from mspl_hff_suffix_sum,
  * branch-major (4,N,n,Ho,Wo); x: the forward input (N,n,H,W); w4: (4,n,3,3); dil: 4 dilations; stride 1|2.
  * gx (N,n,H,W): overwritten, NULL = skip.  gw: 4 device pointers to (n,3,3) buffers that are ACCUMULATED into (zeroed by

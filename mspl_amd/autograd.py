@@ -1539,6 +1539,65 @@ def uw_loss_heads(main, aux, target, class_weights, ce_scale=20.0, out_scale=1.0
     return UWLossHeadsFn.apply(main, aux, target, class_weights, ce_scale, out_scale, root, meters)
 
 
+def nid_heads_plan(B, C, Hm, Wm, H, W, K):
+    """mspl_nid_heads_plan as a dict (band_rows, band_cols, patch_rows, patch_cols, lds_fwd, lds_bwd, bands, fan), or None where the
+    heads kernels do not cover the shape (the caller takes bilinear + NIDLoss.forward)."""
+    import ctypes
+    from ._native import CONSTANTS
+    out = (ctypes.c_int32 * CONSTANTS['NH_PLAN_LEN'])()
+    rc = lib.mspl_nid_heads_plan(int(B), int(C), int(Hm), int(Wm), int(H), int(W), int(K), out)
+    if rc == CONSTANTS['ERR_UNSUPPORTED']:
+        return None
+    check(rc)
+    names = ('band_rows', 'band_cols', 'patch_rows', 'patch_cols', 'lds_fwd', 'lds_bwd', 'bands', 'fan')
+    return dict((n, int(out[CONSTANTS['NH_PLAN_' + n.upper()]])) for n in names)
+
+
+class NIDHeadsFn(torch.autograd.Function):
+    """NIDLoss(image_bin=K, label_bin=label_bin, bw_c, bw_l)(camera, bilinear(main_lo, camera.shape[2:])) from the low-resolution main
+    head (csrc/nid_heads.hip): the histogram kernel, the K x C entropy arithmetic with its closed-form derivative in one small launch,
+    and -- in backward, scaled by the upstream gradient on the device -- the gradient w.r.t. main_lo.  No full-size tensor exists in
+    either direction, and no torch arithmetic runs in between."""
+
+    @staticmethod
+    def forward(ctx, camera, main_lo, K, label_bin, bw_c, bw_l):
+        camera, main_lo = _c(camera.float()), _c(main_lo.float())
+        B, C, Hm, Wm = main_lo.shape
+        H, W = camera.shape[2:]
+        if camera.shape != (B, 3, H, W):
+            raise RuntimeError('mspl_amd: nid_heads expects camera (B,3,H,W) and main_lo (B,C,Hm,Wm), got %s / %s'
+                               % (tuple(camera.shape), tuple(main_lo.shape)))
+        Cl = min(C, K)
+        n_ws = lib.mspl_nid_heads_workspace_floats(C, H, W, K)
+        if n_ws < 0:
+            check(int(n_ws))
+        dev = main_lo.device
+        ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
+        small = torch.empty(K * Cl + K + Cl + 1 + K * Cl + Cl, dtype=torch.float32, device=dev)      # out | loss2 | gjoint | gpl
+        E = K * Cl + K + Cl
+        out, loss2, gj, gpl = small[:E], small[E:E + 1], small[E + 1:E + 1 + K * Cl], small[E + 1 + K * Cl:]
+        check(lib.mspl_nid_heads_fwd(_p(camera), _p(main_lo), B, C, Hm, Wm, H, W, K, float(bw_c), float(bw_l), _p(ws), _p(out), _stream()))
+        check(lib.mspl_nid_finalize(_p(out), K, C, int(label_bin), float(B * H * W), _p(loss2), _p(gj), _p(gpl), _stream()))
+        ctx.save_for_backward(main_lo, ws, gj, gpl)
+        ctx.cfg = (K, float(bw_l), H, W)
+        return loss2[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        main_lo, ws, gj, gpl = ctx.saved_tensors
+        K, bw_l, H, W = ctx.cfg
+        B, C, Hm, Wm = main_lo.shape
+        gmain = torch.zeros_like(main_lo)
+        g = _c(g.to(torch.float32).reshape(1))
+        check(lib.mspl_nid_heads_bwd(_p(main_lo), B, C, Hm, Wm, H, W, K, bw_l, _p(ws), _p(gj), _p(gpl), _p(g), _p(gmain), _stream()))
+        return None, gmain, None, None, None, None
+
+
+def nid_heads(camera, main_lo, K, label_bin, bw_c, bw_l):
+    """The scalar NID term of the reference's train(..., add_loss=NIDLoss(K, label_bin, bw_c, bw_l)) from the low-resolution main head."""
+    return NIDHeadsFn.apply(camera, main_lo, K, label_bin, bw_c, bw_l)
+
+
 class FloodedCEMetersFn(torch.autograd.Function):
     """`loss = criterion(outputs, target).mean(); miou_class.get_iou(outputs, target); loss = (loss - b).abs() + b;
     losses.update(loss.item(), n)` of train_seg_ue (utilities/train_eval_seg.py:202-222) for SegmentationLoss('ce') as one node of two

@@ -12,30 +12,11 @@
 // Backward (w.r.t. the label logits only; the camera image carries no gradient in the reference's use): same staging,
 // G_l[c,p] = sum_k GJ[k,c] P_c[k,p] + Gpl[c], then d lab and the soft-arg-max Jacobian per image.
 #include "common.hpp"
+#include "nid_parts.hpp"
 
 namespace mspl {
 
-constexpr int NID_MAXB = 32;      // image bins and label bins are both limited to 32 (the scripts use 16 / 32 and <= 21)
-
-__device__ __forceinline__ float sigm(float u) { return 1.0f / (1.0f + expf(-u)); }
-
-struct NidG {
-    int B, C, K, Cl, P;           // Cl = min(C, K): label bins that are ever filled
-    float bw_c, bw_l, beta;
-};
-
-__device__ __forceinline__ float soft_arg_max(const float* __restrict__ a, int C, size_t stride, float beta, float eps) {
-    float m = a[0];
-    for (int j = 1; j < C; ++j) m = fmaxf(m, a[j * stride]);
-    float s = 0.f, t = 0.f;
-    for (int j = 0; j < C; ++j) {
-        const float e = expf((a[j * stride] - m) * beta);
-        s += e;
-        t += (e * (float)j);
-    }
-    return t / (s + eps);
-}
-
+// (the sigmoids, the soft-arg-max and the per-position column arithmetic are in nid_parts.hpp, shared with nid_heads.hip)
 __device__ __forceinline__ void stage_columns(const float* __restrict__ cam, const float* __restrict__ lab, const NidG& g, int p,
                                               float* As, float* Ls, bool with_labels) {
     const int t = threadIdx.x;
@@ -43,26 +24,11 @@ __device__ __forceinline__ void stage_columns(const float* __restrict__ cam, con
     if (with_labels)
         for (int c = 0; c < g.Cl; ++c) Ls[c * 256 + t] = 0.f;
     if (p >= g.P) return;
-    const float Lc = 1.0f / (float)g.K;
     for (int b = 0; b < g.B; ++b) {
-        const float* cp = cam + (size_t)b * 3 * g.P + p;
-        const float gray = ((cp[0] + cp[g.P]) + cp[2 * (size_t)g.P]) / 3.0f;
-        for (int k = 0; k < g.K; ++k) {
-            const float mu = Lc * ((float)k + 0.5f);
-            As[k * 256 + t] += sigm((gray - mu + Lc / 2) / g.bw_c) - sigm((gray - mu - Lc / 2) / g.bw_c);
-        }
-        if (with_labels) {
-            const float v = soft_arg_max(lab + (size_t)b * g.C * g.P + p, g.C, (size_t)g.P, g.beta, 1e-12f);
-            for (int c = 0; c < g.Cl; ++c)
-                Ls[c * 256 + t] += sigm((v - (float)c + 0.5f) / g.bw_l) - sigm((v - (float)c - 0.5f) / g.bw_l);
-        }
+        nid_camera_add(As, t, nid_gray(cam + (size_t)b * 3 * g.P + p, (size_t)g.P), g.K, g.bw_c);
+        if (with_labels)
+            nid_label_add(Ls, t, soft_arg_max(lab + (size_t)b * g.C * g.P + p, g.C, (size_t)g.P, g.beta, 1e-12f), g.Cl, g.bw_l);
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
 }
 
 // partial: (blocks, K*Cl + K + Cl)
@@ -73,33 +39,7 @@ __global__ __launch_bounds__(256) void nid_hist_kernel(const float* __restrict__
     float* Ls = lds + g.K * 256;
     stage_columns(cam, lab, g, blockIdx.x * 256 + threadIdx.x, As, Ls, true);
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int E = g.K * g.Cl + g.K + g.Cl;
-    float* out = partial + (size_t)blockIdx.x * E;
-    for (int q = wave; q < E; q += 4) {
-        float s = 0.f;
-        if (q < g.K * g.Cl) {
-            const float* a = As + (q / g.Cl) * 256;
-            const float* l = Ls + (q % g.Cl) * 256;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s = fmaf(a[lane + 64 * j], l[lane + 64 * j], s);
-        } else {
-            const float* a = q < g.K * g.Cl + g.K ? As + (q - g.K * g.Cl) * 256 : Ls + (q - g.K * g.Cl - g.K) * 256;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s += a[lane + 64 * j];
-        }
-        s = wave_sum(s);
-        if (lane == 0) out[q] = s;
-    }
-}
-
-__global__ __launch_bounds__(256) void nid_reduce_kernel(const float* __restrict__ partial, int blocks, int E, double inv_norm,
-                                                         float* __restrict__ out) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    double s = 0.0;
-    for (int b = 0; b < blocks; ++b) s += (double)partial[(size_t)b * E + e];
-    out[e] = (float)(s * inv_norm);
+    nid_partial_sums(As, Ls, g.K, g.Cl, partial + (size_t)blockIdx.x * (g.K * g.Cl + g.K + g.Cl));
 }
 
 // gj: (K, Cl) = dL/d joint, gpl: (Cl) = dL/d p_l, both already divided by norm.  glab: (B, C, P) overwritten.
@@ -115,33 +55,12 @@ __global__ __launch_bounds__(256) void nid_bwd_kernel(const float* __restrict__ 
     stage_columns(cam, lab, g, p, As, Gl, false);
     __syncthreads();
     if (p >= g.P) return;
-    for (int c = 0; c < g.Cl; ++c) {
-        float s = gpl[c];
-        for (int k = 0; k < g.K; ++k) s = fmaf(Gj[k * g.Cl + c], As[k * 256 + t], s);
-        Gl[c * 256 + t] = s;
-    }
+    nid_label_grad_column(Gl, As, Gj, gpl, t, g.K, g.Cl);
     for (int b = 0; b < g.B; ++b) {
         const float* a = lab + (size_t)b * g.C * g.P + p;
         float* ga = glab + (size_t)b * g.C * g.P + p;
-        float m = a[0];
-        for (int j = 1; j < g.C; ++j) m = fmaxf(m, a[(size_t)j * g.P]);
-        float s = 0.f, tt = 0.f;
-        for (int j = 0; j < g.C; ++j) {
-            const float e = expf((a[(size_t)j * g.P] - m) * g.beta);
-            s += e;
-            tt += e * (float)j;
-        }
-        const float S = s + 1e-12f;
-        const float v = tt / S;
-        float dv = 0.f;                                              // dL / d lab
-        for (int c = 0; c < g.Cl; ++c) {
-            const float s1 = sigm((v - (float)c + 0.5f) / g.bw_l), s2 = sigm((v - (float)c - 0.5f) / g.bw_l);
-            dv = fmaf(Gl[c * 256 + t], (s1 * (1.f - s1) - s2 * (1.f - s2)) / g.bw_l, dv);
-        }
-        for (int j = 0; j < g.C; ++j) {
-            const float e = expf((a[(size_t)j * g.P] - m) * g.beta);
-            ga[(size_t)j * g.P] = dv * g.beta * (e / S) * ((float)j - v);
-        }
+        const NidLab r = nid_dlab(a, g.C, (size_t)g.P, Gl, t, g.Cl, g.beta, g.bw_l);
+        for (int j = 0; j < g.C; ++j) ga[(size_t)j * g.P] = nid_dlogit(r, a[(size_t)j * g.P], j, g.beta);
     }
 }
 

@@ -167,7 +167,8 @@ class _NIDHistFn(torch.autograd.Function):
 class NIDLoss(nn.Module):
     """loss_fns/segmentation_loss.py:54-121: (NID(camera grey levels, soft-arg-max labels) - 0.95) * 20.  The soft histograms
     run in two HIP kernels (nid.hip); the K x C entropy arithmetic below is the reference's, on tiny device tensors.  The
-    reference's hard-coded `.to('cuda')` calls have no counterpart (tensors stay on the inputs' device)."""
+    reference's hard-coded `.to('cuda')` calls have no counterpart (tensors stay on the inputs' device).  `at_heads` is the same
+    loss on the up-sampled low-resolution main head, for the training step that never materialises the full-size logits."""
 
     def __init__(self, image_bin=16, label_bin=4, bw_camera=0.005, bw_label=0.001):
         super().__init__()
@@ -190,3 +191,19 @@ class NIDLoss(nn.Module):
         p_l = p_l / p_l.sum()
         nid = self.nid(p_cl, p_c.reshape(-1, 1), p_l.reshape(-1, 1))
         return (nid - 0.95) * 20
+
+    def heads_supported(self, camera, main_lo):
+        """Whether `at_heads` covers these shapes (mspl_nid_heads_plan): at most 32 bins and classes, a head no larger than the image,
+        columns and patches within the LDS budget.  Otherwise: forward(camera, bilinear(main_lo, camera.shape[2:]))."""
+        from . import autograd as ag
+        B, C, Hm, Wm = main_lo.shape
+        return self.C <= C and ag.nid_heads_plan(B, C, Hm, Wm, camera.shape[2], camera.shape[3], self.K) is not None
+
+    def at_heads(self, camera, main_lo):
+        """forward(camera, F.interpolate(main_lo, camera.shape[2:], mode='bilinear', align_corners=True)) from the decoder's
+        low-resolution main head (espdnet_ue.py:301), in three launches forward and one backward (csrc/nid_heads.hip): the full-size
+        logits and their gradient never exist, and the entropy arithmetic of `forward` runs in one small double-precision kernel."""
+        from . import autograd as ag
+        if main_lo.shape[1] < self.C:
+            raise RuntimeError('mspl_amd: NIDLoss(label_bin=%d) got logits with %d classes' % (self.C, main_lo.shape[1]))
+        return ag.nid_heads(camera, main_lo, self.K, self.C, float(self.bw_camera), float(self.bw_label))

@@ -91,7 +91,11 @@ def _fast_path(model, criterion, optimizer, args, add_loss):
     from . import losses
     if _FORCE_RESTATED or getattr(args, 'model', None) != 'espdnetue' or getattr(args, 'use_depth', False):
         return False
-    if not getattr(args, 'use_uncertainty', False) or add_loss is not None or model.training:
+    if not getattr(args, 'use_uncertainty', False) or model.training:
+        return False
+    # the additional loss of --use-nid: the drop-in NIDLoss itself (not a subclass, not another callable) with one label bin per
+    # class of the model; anything else runs the reference body
+    if add_loss is not None and (type(add_loss) is not losses.NIDLoss or add_loss.C != getattr(model, 'classes', None)):
         return False
     if type(criterion) is not losses.UncertaintyWeightedSegmentationLoss:
         return False
@@ -101,10 +105,17 @@ def _fast_path(model, criterion, optimizer, args, add_loss):
     return not g.get('amsgrad', False) and not g.get('maximize', False)
 
 
-def _train_fast(trainloader, model, criterion, device, optimizer, tot_iter, args, meters):
+def _nid_key(add_loss):
+    """What a captured step froze of its additional loss: None without one, else the NIDLoss settings."""
+    return None if add_loss is None else (add_loss.K, add_loss.C, float(add_loss.bw_camera), float(add_loss.bw_label))
+
+
+def _train_fast(trainloader, model, criterion, device, optimizer, tot_iter, args, meters, add_loss=None):
     """The step loop on training.GraphedTrainStep: no .item(), no .cpu(), no synchronize inside.  The caller's optimizer never
     steps (its state stays empty); its hyper-parameters are read into the FlatAdam of the graphed step and its learning rate is
-    kept current.  One graphed step per model is kept on the model object and reused across epochs and rounds."""
+    kept current.  One graphed step per model is kept on the model object and reused across epochs and rounds.  It is keyed on its
+    meters and on the additional loss it was captured with: a model whose step was captured without the NID term (or with other
+    NIDLoss settings) and that is then trained with it raises -- the captured graph cannot change what it computes."""
     import weakref
     from . import training
     g = optimizer.param_groups[0]
@@ -118,11 +129,17 @@ def _train_fast(trainloader, model, criterion, device, optimizer, tot_iter, args
         if gs is None:
             # the first batch shapes the capture and is NOT applied by it (consume_first_batch=False)
             gs = training.GraphedTrainStep(model, images, labels, criterion.class_weights, None, lr=lr, weight_decay=g['weight_decay'],
-                                           lanes=int(getattr(args, 'train_lanes', 2)), meters=meters, consume_first_batch=False)
+                                           lanes=int(getattr(args, 'train_lanes', 2)), meters=meters, consume_first_batch=False,
+                                           add_loss=add_loss)
             state['step'] = gs
             state['optimizer'] = None
         if gs.meters is not meters:
             raise RuntimeError('mspl_amd.script.train: the graphed step of this model was captured with other meters')
+        if _nid_key(gs.add_loss) != _nid_key(add_loss):
+            raise RuntimeError('mspl_amd.script.train: the graphed step of this model was captured %s and is now called %s; a captured '
+                               'step cannot change its loss (train a fresh model object, or keep add_loss the same across epochs)'
+                               % tuple('without an additional loss' if k is None else 'with NIDLoss(image_bin=%d, label_bin=%d, bw_camera=%g, '
+                                       'bw_label=%g)' % k for k in (_nid_key(gs.add_loss), _nid_key(add_loss))))
         if state.get('optimizer') is None or state['optimizer']() is not optimizer:
             # a new optimizer object (one per round, :594-598) starts as a fresh torch.optim.Adam would
             gs.reset_optimizer(lr, g['betas'], g['eps'], g['weight_decay'])
@@ -133,7 +150,7 @@ def _train_fast(trainloader, model, criterion, device, optimizer, tot_iter, args
         if tuple(images.shape) == tuple(gs.images.shape):
             gs(images, labels)
         else:                                                    # the loader has no drop_last: same FlatAdam, same meters, eager
-            training.train_step(model, images, labels, gs.cw, gs.optimizer, None, ce_scale=gs.ce_scale, meters=meters)
+            training.train_step(model, images, labels, gs.cw, gs.optimizer, None, ce_scale=gs.ce_scale, meters=meters, add_loss=add_loss)
     return images, labels, None
 
 
@@ -182,7 +199,7 @@ def _train(namespace, trainloader, model, criterion, device, interp, optimizer, 
         meters = state['meters'] = training.TrainMeters(4, device)          # MIOU(num_classes=4), :971
     meters.reset()
     if _fast_path(model, criterion, optimizer, args, add_loss):
-        images, labels, depths = _train_fast(trainloader, model, criterion, device, optimizer, tot_iter, args, meters)
+        images, labels, depths = _train_fast(trainloader, model, criterion, device, optimizer, tot_iter, args, meters, add_loss)
     else:
         images, labels, depths = _train_restated(trainloader, model, criterion, device, optimizer, tot_iter, args, add_loss, meters)
     r = meters.read()                   # the epoch's one device-to-host copy
@@ -215,10 +232,12 @@ def train(trainloader, model, criterion, device, interp, optimizer, tot_iter, ro
           class_encoding, writer_idx, class_weights=None, writer=None, add_loss=None):
     """uest_seg_multi_os.py:958-1089 with its own signature; returns writer_idx + 1.  `interp` is ignored (:986), `round_idx`,
     `epoch_idx`, `logger`, `metric` and `class_weights` are accepted and unused, as there.  With the shipped settings (espdnetue, no
-    depth, --use-uncertainty, no additional loss, a model in eval() mode, the drop-in UncertaintyWeightedSegmentationLoss, one-group
-    torch.optim.Adam) the steps run on training.GraphedTrainStep with `args.train_lanes` (default 2) micro-batch lanes and the
-    meters are taken inside the loss kernel; the caller's Adam then never steps and holds no state.  Everything else runs the
-    reference body on the drop-in modules."""
+    depth, --use-uncertainty, a model in eval() mode, the drop-in UncertaintyWeightedSegmentationLoss, one-group torch.optim.Adam)
+    the steps run on training.GraphedTrainStep with `args.train_lanes` (default 2) micro-batch lanes and the meters are taken
+    inside the loss kernel; the caller's Adam then never steps and holds no state.  `add_loss` (--use-nid) may be None or the drop-in
+    NIDLoss with label_bin equal to the model's class count: its term is then taken from the low-resolution main head inside the
+    same graph (NIDLoss.at_heads), on ONE lane whatever `args.train_lanes` says (the NID histogram couples the images of a batch).
+    Everything else runs the reference body on the drop-in modules."""
     return _train(None, trainloader, model, criterion, device, interp, optimizer, tot_iter, round_idx, epoch_idx, args, logger, metric,
                   class_encoding, writer_idx, class_weights, writer, add_loss)
 

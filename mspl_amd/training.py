@@ -85,20 +85,48 @@ class TrainMeters:
                 'union': a[1] + a[2] - a[0] + self.steps * 1e-6, 'areas': a, 'steps': self.steps}
 
 
-def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=False, meters=None):
+def _additional_loss(add_loss, images, main, pred, meters):
+    """loss2 = add_loss(images, pred) (uest_seg_multi_os.py:1027-1030) and its two meter adds on the device: meter[1] += loss2
+    (nid_losses.update(loss2.item(), 1)) and meter[0] += B * loss2 (losses.update(loss.item(), B) at :1037 sees the loss after `loss
+    += loss2`).  A losses.NIDLoss takes the low-resolution main head `main` where its heads kernels cover the shape; otherwise (and
+    for any other callable) the full-size `pred`, up-sampled here when only `main` is given."""
+    from . import losses
+    if main is not None and type(add_loss) is losses.NIDLoss and add_loss.heads_supported(images, main):
+        loss2 = add_loss.at_heads(images, main)
+    else:
+        loss2 = add_loss(images, pred if pred is not None else ag.bilinear(main, tuple(images.shape[2:])))
+    if meters is not None:
+        l2 = loss2.detach().double()
+        meters.meter[0] += l2 * float(images.shape[0])
+        meters.meter[1] += l2
+    return loss2
+
+
+def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=False, meters=None, add_loss=None):
     """model forward + uest loss (uest_seg_multi_os.py:1010-1023) on device class weights `cw`.  A model that exposes its decoder
     outputs (`forward_lowres`: main at H/2, auxiliary at H/4) gets the loss taken at head resolution -- the up-sampling of
     espdnet_ue.py:301-302 happens inside the loss kernel (ag.uw_loss_heads), same value and gradients; any other model is called as
     the reference calls it and the loss takes its two full-size outputs.  meters: a TrainMeters that receives this batch's area
-    histograms and loss * batch size (a lane passes out_scale = 1 / lanes and adds its share)."""
+    histograms and loss * batch size (a lane passes out_scale = 1 / lanes and adds its share).
+
+    add_loss: the additional loss of train(..., add_loss=...) (:1027-1030), added to the returned loss; a losses.NIDLoss is taken from
+    the low-resolution main head too (NIDLoss.at_heads) where the plan of its kernels covers the shape.  It sees all images of a
+    batch at one pixel position together, so it goes with out_scale = 1 only (no micro-batch lanes)."""
+    if add_loss is not None and out_scale != 1.0:
+        raise RuntimeError('mspl_amd.training.forward_loss: an additional loss couples the images of a batch; it cannot be split '
+                           'into micro-batch lanes (out_scale = %g)' % out_scale)
     lowres = getattr(model, 'forward_lowres', None) if _LOSS_AT_HEADS else None
+    main = None
     if lowres is not None:
         main, aux = lowres(images)
         if aux is None:
             raise RuntimeError('mspl_amd.training.forward_loss: %s returns one head; the uest loss needs the auxiliary head of a '
                                'two-head model' % type(model).__name__)
         if ag.uw_loss_heads_supported(main.shape[1]):
-            return ag.uw_loss_heads(main, aux, labels, cw, ce_scale, out_scale, root, meters)
+            loss = ag.uw_loss_heads(main, aux, labels, cw, ce_scale, out_scale, root, meters)
+            if add_loss is not None:
+                loss = loss + _additional_loss(add_loss, images, main, None, meters)
+            return loss
         size = tuple(images.shape[2:])
         pred, aux = ag.bilinear(main, size), ag.bilinear(aux, size)
     else:
@@ -106,6 +134,8 @@ def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=F
     loss = ag.uw_loss(pred, aux, labels, cw, ce_scale, out_scale, root)
     if meters is not None:      # the three-step form: the existing area kernel on the full-size main head, loss * B added on the device
         meters.add(pred, labels, loss, images.shape[0] / out_scale)
+    if add_loss is not None:
+        loss = loss + _additional_loss(add_loss, images, main, pred, meters)
     return loss
 
 
@@ -158,12 +188,13 @@ def adjust_learning_rate(optimizer, i_iter, tot_iter, base_lr, power=0.0):
 
 
 def train_step(model, images, labels, class_weights, optimizer=None, ignore_idx=None, lr=5e-4, weight_decay=5e-4,
-               ce_scale=20.0, meters=None):
+               ce_scale=20.0, meters=None, add_loss=None):
     """One optimisation step; returns (loss tensor, optimizer).  Pass optimizer=None on the first call: it is built
-    after the first backward (which reveals the gradient-bearing parameters).  meters: a TrainMeters the step is added to."""
+    after the first backward (which reveals the gradient-bearing parameters).  meters: a TrainMeters the step is added to.
+    add_loss: the additional loss of train(..., add_loss=...), see forward_loss."""
     def loss_fn():
         return forward_loss(model, images, labels, _device_class_weights(class_weights, images.device, ignore_idx), ce_scale,
-                            meters=meters), None
+                            meters=meters, add_loss=add_loss), None
 
     loss, _, optimizer = run_step(model, optimizer, images.shape[0], loss_fn,
                                   lambda: FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay), meters)
@@ -198,26 +229,32 @@ class GraphedTrainStep(GraphedStep):
     graph did not).  Same step: BatchNorm is frozen, the loss is a plain mean over the pixels of the batch (K11: 1 / (N*H*W)), so
     each lane back-propagates loss_lane / L and every parameter-gradient kernel adds into the shared flat gradient buffer with
     atomics (autograd.grad_sinks); only the floating-point summation order differs.  A parameter whose gradient would go through
-    autograd's (non-atomic) AccumulateGrad in a lane is refused at construction."""
+    autograd's (non-atomic) AccumulateGrad in a lane is refused at construction.
+
+    add_loss: the additional loss of train(..., add_loss=...) (forward_loss), captured inside the graph.  With one the step runs
+    lanes = 1 whatever is asked: NIDLoss's joint histogram sums the images of a batch per pixel position BEFORE its outer product, so
+    it has cross terms between the images of a batch, and micro-batch lanes would compute another loss."""
 
     def __init__(self, model, images, labels, class_weights, ignore_idx=None, lr=5e-4, weight_decay=5e-4, ce_scale=20.0, lanes=1,
-                 meters=None, consume_first_batch=True):
+                 meters=None, consume_first_batch=True, add_loss=None):
         """meters: a TrainMeters captured inside the graph(s) -- every lane adds into the same buffers; it is reset when the
         constructor returns.  consume_first_batch=False: the construction batch only shapes the capture -- the parameters are put
         back to their values on entry, both Adam moments, the step count and the meters are zeroed, so the first call is step 1 (a
         training loop applies each batch exactly once; the default applies the construction batch twice: an eager step, then the
         captured one)."""
-        self.model, self.meters = model, meters
+        self.model, self.meters, self.add_loss = model, meters, add_loss
         self.cw = _device_class_weights(class_weights, images.device, ignore_idx)
         self.ce_scale = ce_scale
-        self.lanes = lanes if (lanes > 1 and images.shape[0] % lanes == 0) else 1
+        self.lanes = lanes if (lanes > 1 and images.shape[0] % lanes == 0 and add_loss is None) else 1
         # (the eager step gets the caller's class weights and no meters; the capture reads this object's own `cw`)
         self._build([('images', images), ('labels', labels.to(torch.int64))],
-                    lambda: train_step(model, self.images, self.labels, class_weights, None, ignore_idx, lr, weight_decay, ce_scale)[1],
+                    lambda: train_step(model, self.images, self.labels, class_weights, None, ignore_idx, lr, weight_decay, ce_scale,
+                                       add_loss=add_loss)[1],
                     consume_first_batch)
 
     def _lane_loss(self, images, labels, out_scale=1.0):
-        return forward_loss(self.model, images, labels, self.cw, self.ce_scale, out_scale=out_scale, root=True, meters=self.meters)
+        return forward_loss(self.model, images, labels, self.cw, self.ce_scale, out_scale=out_scale, root=True, meters=self.meters,
+                            add_loss=self.add_loss)
 
     def _loss(self):
         return self._lane_loss(self.images, self.labels), None
