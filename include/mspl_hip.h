@@ -272,6 +272,49 @@ int mspl_fusion_gate_fwd(const float* z, const float* rgb, const float* depth, i
 int mspl_fusion_gate_bwd(const float* z, const float* rgb, const float* depth, const float* gy, int64_t count,
                          float* gz, float* grgb, float* gdepth, void* stream);
 
+/* The trainable gate as ONE launch (nn_layers/fusion_gate.py:27-41): the 1x1 convolution over cat(rgb, depth), the sigmoid and the
+ * blend, without the concatenation and without a stored pre-sigmoid tensor on the inference path.
+ *     z = W[:, :C] . rgb + W[:, C:] . depth,   g = sigmoid(z),   out = rgb*g + depth*(1-g)
+ * rgb, depth, out: (N,C,HW); w: (C, 2C), the module's weight as stored; z: NULL (inference) or (N,C,HW), which then receives the
+ * pre-sigmoid value for the backward.  The product runs on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32, a k-ordered
+ * fmaf chain) as two K = C passes over one accumulator set -- the staged weight tile is rows x C, never rows x 2C -- and the blend
+ * re-reads its operands right after the product has used the same lines (no separate pass); sigmoid and blend are those of
+ * mspl_fusion_gate_fwd.
+ * Served (mspl_fusion_gate_conv_fits returns 1): C % 32 == 0, 32 <= C <= 512, N*C*HW < 2^30 and either HW % 4 == 0 (the matrix-core
+ * form, 16-byte accesses, 16-byte aligned operands) or N*HW <= 4096 (other plane sizes -- level 4 of a 32x48 input has 6 pixels per
+ * plane -- are SERVED by a scalar form up to that size: one thread per output element, the same k-ordered fmaf chain, 4-byte
+ * accesses).  Anything else is declined: _fwd and _bwd_weight return MSPL_ERR_UNSUPPORTED with nothing launched, as the matrix-core
+ * form does for operands that are not 16-byte aligned, and callers run mspl_conv1x1_fwd (twice) + mspl_fusion_gate_fwd. */
+int mspl_fusion_gate_conv_fits(int32_t N, int32_t C, int32_t HW);
+int mspl_fusion_gate_conv_fwd(const float* rgb, const float* depth, const float* w, int32_t N, int32_t C, int32_t HW, float* z,
+                              float* out, void* stream);
+/* Weight gradient of the gate's convolution: gw (C, 2C) (+)= gz . [rgb; depth]^T over N*HW, both column halves from one read of
+ * gz (a wave holds the rgb and the depth 32x32 tile of the same rows).  Partial tiles are combined with float atomics: accumulate == 0
+ * zeroes gw first (an async memset node), accumulate != 0 adds to what is there -- gw may be the parameter's gradient buffer that
+ * concurrent micro-batch lanes share.  Same served shapes as _fwd. */
+int mspl_fusion_gate_conv_bwd_weight(const float* gz, const float* rgb, const float* depth, int32_t N, int32_t C, int32_t HW,
+                                     int32_t accumulate, float* gw, void* stream);
+/* What the two launchers decide for a shape, each from the one host function its launcher calls (no device call, no state).
+ * _plan: out[MSPL_FGC_PLAN_LEN].  _bwd_weight_plan: *form, *parts = waves that share one pair of 32x32 tiles (wave s takes the
+ * 64-pixel groups s, s + parts, ... of the flattened (image, pixel group) range) and *ngroups = the number of those groups. */
+typedef enum {
+    MSPL_FGC_FORM_MFMA_X4 = 1,         /* matrix cores, four pixels per lane, 16-byte accesses */
+    MSPL_FGC_FORM_SCALAR = 2           /* vector unit, one output element per thread: HW % 4 != 0 and N*HW <= 4096 (rows, pixels, LDS: 0) */
+} mspl_fusion_gate_conv_form_t;
+typedef enum {
+    MSPL_FGC_WGRAD_MFMA_PAIR = 1,      /* matrix cores, one wave = the rgb and the depth tile of 32 rows, fragments straight from memory */
+    MSPL_FGC_WGRAD_SCALAR = 2          /* vector unit, one element of gw per thread over the whole range: parts = 1, ngroups = 0 */
+} mspl_fusion_gate_conv_wgrad_form_t;
+#define MSPL_FGC_PLAN_FORM 0            /* an mspl_fusion_gate_conv_form_t */
+#define MSPL_FGC_PLAN_ROWS 1            /* output rows per workgroup (32 or 64): the row-chunk seam */
+#define MSPL_FGC_PLAN_PIXELS 2          /* pixels of the flattened (image, pixel) axis per workgroup */
+#define MSPL_FGC_PLAN_WAVE_PIXELS 3     /* ... per wave (128) */
+#define MSPL_FGC_PLAN_LDS_BYTES 4       /* dynamic LDS of the launch: one source's weight tile */
+#define MSPL_FGC_PLAN_GRID_X 5
+#define MSPL_FGC_PLAN_LEN 6
+int mspl_fusion_gate_conv_plan(int32_t N, int32_t C, int32_t HW, int32_t* out);
+int mspl_fusion_gate_conv_bwd_weight_plan(int32_t N, int32_t C, int32_t HW, int32_t* form, int32_t* parts, int32_t* ngroups);
+
 /* mspl_avgpool3x3s2_fwd that also leaves partial plane sums of its input: psum (N*C, nblk) with nblk =
  * mspl_avgpool3x3s2_psum_blocks(H, W) (one partial per workgroup of a plane, every slot written, summed in order by the
  * consumer: deterministic), and the EfficientPWConv gate computed from them: gate (N,Cout) = sigmoid(W (Cout,Cin) . sum_j psum / HW).

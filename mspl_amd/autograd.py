@@ -1196,6 +1196,48 @@ class FusionGateFn(torch.autograd.Function):
         return None, grgb, gdepth
 
 
+class FusionGateConvFn(torch.autograd.Function):
+    """The trainable FusionGate as ONE node (nn_layers/fusion_gate.py:27-41): out = rgb*g + depth*(1-g), g = sigmoid(w . cat(rgb, depth)),
+    w (C, 2C, 1, 1) as the module stores it.  Forward: one launch (mspl_fusion_gate_conv_fwd) that also leaves the pre-sigmoid z.
+    Backward: the blend's backward kernel gives gz and the direct parts of d rgb / d depth; the convolution's data gradients are two 1x1
+    launches over the two row halves of the transposed weight (each contiguous), with the direct part added in the epilogue; the weight
+    gradient is one launch for both column halves, written where the weight's GradDst says -- there is no concatenation, no weight
+    slice and so nothing between the parameter and its sink, at any level.  Callers check ops.fusion_gate_conv_fits first."""
+
+    @staticmethod
+    def forward(ctx, rgb, depth, w):
+        rgb, depth, w = _c(rgb), _c(depth), _c(w)
+        res = ops.fusion_gate_conv(rgb, depth, w, keep_z=True)
+        if res is None:
+            raise RuntimeError('mspl_amd: FusionGateConvFn: shape %s is not served by mspl_fusion_gate_conv_fwd' % (tuple(rgb.shape),))
+        out, z = res
+        ctx.save_for_backward(z, rgb, depth, w)
+        ctx.g_w = GradDst(w)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        z, rgb, depth, w = ctx.saved_tensors
+        gy = _c(gy)
+        N, C, H, W = rgb.shape
+        gz, grgb, gdepth = torch.empty_like(gy), torch.empty_like(gy), torch.empty_like(gy)
+        check(lib.mspl_fusion_gate_bwd(_p(z), _p(rgb), _p(depth), _p(gy), gy.numel(), _p(gz), _p(grgb), _p(gdepth), _stream()))
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            wt = _transposed_weights(w, 1, 1)                           # (2C, C, 1, 1): rows [0, C) = w[:, :C]^T, rows [C, 2C) = w[:, C:]^T
+            grgb = ops.conv1x1(gz, wt[:C], 1, Epi(pre_add=grgb)) if ctx.needs_input_grad[0] else None
+            gdepth = ops.conv1x1(gz, wt[C:], 1, Epi(pre_add=gdepth)) if ctx.needs_input_grad[1] else None
+        else:
+            grgb = gdepth = None
+        if ctx.needs_input_grad[2]:
+            check(lib.mspl_fusion_gate_conv_bwd_weight(_p(gz), _p(rgb), _p(depth), N, C, H * W, int(ctx.g_w.is_sink),
+                                                       _p(ctx.g_w.buf(zeroed=False)), _stream()))
+        return grgb, gdepth, ctx.g_w.result()
+
+
+def fusion_gate_conv(rgb, depth, w):
+    return FusionGateConvFn.apply(rgb, depth, w)
+
+
 class ChannelScaleFn(torch.autograd.Function):
     """y[n,c,:,:] * gate[n,c]."""
 

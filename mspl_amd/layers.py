@@ -226,6 +226,9 @@ _FUSED_HEAD_CLASSIFIER = os.environ.get('MSPL_HEAD_CLASSIFIER', '1') != '0'
 # inference: the pyramid kernel's streaming form reads its stencil tables from memory (built once per map geometry) instead of
 # computing them in every workgroup, and walks longer row segments (ops.pyr_stream_tables); same output bits
 _PYR_STREAM_TABLES = os.environ.get('MSPL_PYR_STREAM_TABLES', '1') != '0'
+# RGB-D: the trainable FusionGate (its 1x1 over cat(rgb, depth), sigmoid and blend) as one launch and, on the training path, one autograd
+# node (ops.fusion_gate_conv / autograd.FusionGateConvFn); 0: two conv1x1 launches + the blend kernel, cat + conv when training
+_FUSED_FUSION_GATE = os.environ.get('MSPL_FUSION_GATE', '1') != '0'
 _FUSED_DEC_MERGE = True         # inference: skip 3x3 + up-merge + the next pyramid block's projection as one launch (ops.decoder_merge)
 _FUSED_NEXT_PROJ = os.environ.get('MSPL_EESP_NEXT', '1') != '0'   # ... and the following block's proj_1x1 inside that launch
 _FUSED_EESP_TRAIN = os.environ.get('MSPL_FUSED_EESP_TRAIN', '1') != '0'  # EESP block as one autograd node (frozen BatchNorm)

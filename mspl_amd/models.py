@@ -21,6 +21,7 @@ from torch.nn import init
 
 from . import ops
 from . import autograd as ag
+from . import layers
 from .layers import (C, CBR, DownSampler, EESP, EfficientPWConv, EfficientPyrPool, ImagePyramid, _training_path, cached, run_eesp_chain,
                      decoder_stage_fusable, decoder_stage_fused,
                      decoder_merge, fork, join, wait_mark)
@@ -96,8 +97,12 @@ _GATE_CAT_MAX_K = 512         # training path: widest concatenation the gate's 1
 
 class FusionGate(nn.Module):
     """RGB-D fusion gate (nn_layers/fusion_gate.py:11-47): out = rgb*w + depth*(1-w), w = sigmoid(conv_1x1(cat(rgb, depth))),
-    or rgb + depth when not trainable.  The concatenation is never materialised on the inference path: the 1x1 runs as two
-    matrix-core launches over the two halves of the weight (the second accumulates onto the first), then one blend kernel.
+    or rgb + depth when not trainable.  The trainable gate is ONE launch (ops.fusion_gate_conv: the 1x1 as two K = c passes over the
+    weight halves on one accumulator set, sigmoid and blend in the epilogue) and, when gradients are enabled, one autograd node
+    (autograd.FusionGateConvFn: the weight's gradient goes straight to its sink at every level).  Where the library declines the
+    shape, or with layers._FUSED_FUSION_GATE off (MSPL_FUSION_GATE=0): two matrix-core launches over the two halves of the weight (the
+    second accumulates onto the first), then one blend kernel; cat + conv when training.  The concatenation is never materialised
+    on the inference path.
     The reference's hard-coded `.to('cuda')` (:38) has no counterpart: everything stays on the inputs' device."""
 
     def __init__(self, nchannel, is_trainable=True):
@@ -112,8 +117,15 @@ class FusionGate(nn.Module):
             raise RuntimeError('mspl_amd: FusionGate(%d) got rgb %s and depth %s'
                                % (self.nchannel, tuple(rgb.shape), tuple(depth.shape)))
         w = self.conv_1x1.conv.weight
+        c = self.nchannel
+        # the one-launch gate (ops.fusion_gate_conv, autograd.FusionGateConvFn) where the library serves the shape; an operand off a
+        # 16-byte boundary (an unusual view) is what the launcher would decline: both paths then take the launches below
+        fused = (self.is_trainable and layers._FUSED_FUSION_GATE and rgb.dim() == 4
+                 and ops.fusion_gate_conv_fits(rgb.shape[0], c, rgb.shape[2] * rgb.shape[3])
+                 and (rgb.data_ptr() | depth.data_ptr() | w.data_ptr()) % 16 == 0)
         if _training_path():
-            c = self.nchannel
+            if fused:
+                return ag.fusion_gate_conv(rgb, depth, w)
             if not self.is_trainable:
                 z = None
             elif 2 * c > _GATE_CAT_MAX_K:
@@ -125,7 +137,10 @@ class FusionGate(nn.Module):
             return ag.FusionGateFn.apply(z, rgb, depth)
         if not self.is_trainable:
             return ops.fusion_gate(None, rgb, depth)
-        c = self.nchannel
+        if fused:
+            out = ops.fusion_gate_conv(rgb, depth, w)
+            if out is not None:                   # (None: declined after all, e.g. a misaligned view -- today's launches)
+                return out
         w_rgb, w_d = cached(self, 'halves', [w], lambda: (w[:, :c].contiguous(), w[:, c:].contiguous()))
         z = ops.conv1x1(rgb, w_rgb)
         z = ops.conv1x1(depth, w_d, ep=ops.Epi(pre_add=z))

@@ -570,6 +570,55 @@ def fusion_gate(z, rgb, depth):
     return out
 
 
+def fusion_gate_conv_fits(N, C, HW):
+    """True for the shapes mspl_fusion_gate_conv_fwd / _bwd_weight serve (the library's own predicate)."""
+    return bool(lib.mspl_fusion_gate_conv_fits(int(N), int(C), int(HW)))
+
+
+def fusion_gate_conv_plan(N, C, HW):
+    """What mspl_fusion_gate_conv_fwd launches for a shape (mspl_fusion_gate_conv_plan, the launcher's own host function; no device
+    call) -> dict form / rows / pixels / wave_pixels / lds_bytes / grid_x, or None for a shape it declines."""
+    out = (ctypes.c_int32 * nat.FGC_PLAN_LEN)()
+    rc = lib.mspl_fusion_gate_conv_plan(int(N), int(C), int(HW), out)
+    if rc == nat.ERR_UNSUPPORTED:
+        return None
+    check(rc)
+    return {n.lower(): int(out[getattr(nat, 'FGC_PLAN_' + n)]) for n in ('FORM', 'ROWS', 'PIXELS', 'WAVE_PIXELS', 'LDS_BYTES', 'GRID_X')}
+
+
+def fusion_gate_conv_bwd_weight_plan(N, C, HW):
+    """-> dict form / parts / ngroups of mspl_fusion_gate_conv_bwd_weight (wave s of a tile pair takes the 64-pixel groups s, s + parts,
+    ... of the ngroups groups of the flattened (image, pixel group) range), or None for a shape it declines."""
+    form, parts, ngroups = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = lib.mspl_fusion_gate_conv_bwd_weight_plan(int(N), int(C), int(HW), ctypes.byref(form), ctypes.byref(parts), ctypes.byref(ngroups))
+    if rc == nat.ERR_UNSUPPORTED:
+        return None
+    check(rc)
+    return {'form': form.value, 'parts': parts.value, 'ngroups': ngroups.value}
+
+
+def fusion_gate_conv(rgb, depth, w, keep_z=False):
+    """The trainable FusionGate in one launch: out = rgb*g + depth*(1-g), g = sigmoid(w[:, :C] . rgb + w[:, C:] . depth); w (C, 2C[,1,1])
+    as the module stores it.  Returns out -- (out, z) with keep_z, z the pre-sigmoid tensor the backward needs -- or None when the
+    library declines the shape (MSPL_ERR_UNSUPPORTED, nothing launched): the caller then runs conv1x1 twice and fusion_gate."""
+    rgb, depth, w = _f32(rgb, 'rgb'), _f32(depth, 'depth'), _f32(w, 'w')
+    if rgb.shape != depth.shape or rgb.dim() != 4:
+        raise RuntimeError('mspl_amd: fusion_gate_conv operands differ in shape: %s %s' % (tuple(rgb.shape), tuple(depth.shape)))
+    N, C = rgb.shape[:2]
+    HW = rgb.shape[2] * rgb.shape[3]
+    if w.numel() != 2 * C * C or w.shape[0] != C:
+        raise RuntimeError('mspl_amd: fusion_gate_conv weight %s does not match C=%d' % (tuple(w.shape), C))
+    if not fusion_gate_conv_fits(N, C, HW):
+        return None
+    out = torch.empty_like(rgb)
+    z = torch.empty_like(rgb) if keep_z else None
+    rc = lib.mspl_fusion_gate_conv_fwd(_p(rgb), _p(depth), _p(w), N, C, HW, None if z is None else _p(z), _p(out), _stream())
+    if rc == nat.ERR_UNSUPPORTED:
+        return None
+    check(rc)
+    return (out, z) if keep_z else out
+
+
 def pyr_down_prep_fits(shape, sizes):
     """True when pyr_down_prep can stage a row band of an (N,P,h,w) map with these branch sizes in LDS
     (else: adaptive_avgpool + conv3x3 per branch)."""

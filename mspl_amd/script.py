@@ -87,11 +87,14 @@ _FORCE_RESTATED = False         # tests: send a call that qualifies for the grap
 
 def _fast_path(model, criterion, optimizer, args, add_loss):
     """The settings of the shipped espdnet_greenhouse_uest_multi_os.sh: everything the graphed step (frozen BatchNorm, the uest
-    loss at head resolution, Adam on flat buffers) computes."""
+    loss at head resolution, Adam on flat buffers) computes.  RGB-D batches (`--use-depth true`) qualify as well: the step takes the
+    depth batch as a third static tensor.  RGB-D together with an additional loss (--use-nid) keeps the restated body."""
     from . import losses
-    if _FORCE_RESTATED or getattr(args, 'model', None) != 'espdnetue' or getattr(args, 'use_depth', False):
+    if _FORCE_RESTATED or getattr(args, 'model', None) != 'espdnetue':
         return False
     if not getattr(args, 'use_uncertainty', False) or model.training:
+        return False
+    if getattr(args, 'use_depth', False) and add_loss is not None:
         return False
     # the additional loss of --use-nid: the drop-in NIDLoss itself (not a subclass, not another callable) with one label bin per
     # class of the model; anything else runs the reference body
@@ -115,22 +118,27 @@ def _train_fast(trainloader, model, criterion, device, optimizer, tot_iter, args
     steps (its state stays empty); its hyper-parameters are read into the FlatAdam of the graphed step and its learning rate is
     kept current.  One graphed step per model is kept on the model object and reused across epochs and rounds.  It is keyed on its
     meters and on the additional loss it was captured with: a model whose step was captured without the NID term (or with other
-    NIDLoss settings) and that is then trained with it raises -- the captured graph cannot change what it computes."""
+    NIDLoss settings) and that is then trained with it raises -- the captured graph cannot change what it computes.  The same holds
+    for the depth batch of `args.use_depth` (batch[2]): a step captured with one must be called with one.  Returns the last batch's
+    (images, labels, depths) for the visualisation hook."""
     import weakref
     from . import training
     g = optimizer.param_groups[0]
     state = model.__dict__.setdefault('_mspl_train_loop', {})
-    images = labels = None
+    use_depth = bool(getattr(args, 'use_depth', False))
+    images = labels = depths = None
     for i_iter, batch in enumerate(trainloader):
         images = batch[0].to(device)
         labels = batch[1].to(device)
+        if use_depth:
+            depths = batch[2].to(device)
         lr = training.adjust_learning_rate(optimizer, i_iter, tot_iter, args.learning_rate, args.power)        # :982
         gs = state.get('step')
         if gs is None:
             # the first batch shapes the capture and is NOT applied by it (consume_first_batch=False)
             gs = training.GraphedTrainStep(model, images, labels, criterion.class_weights, None, lr=lr, weight_decay=g['weight_decay'],
                                            lanes=int(getattr(args, 'train_lanes', 2)), meters=meters, consume_first_batch=False,
-                                           add_loss=add_loss)
+                                           add_loss=add_loss, depth=depths)
             state['step'] = gs
             state['optimizer'] = None
         if gs.meters is not meters:
@@ -147,11 +155,16 @@ def _train_fast(trainloader, model, criterion, device, optimizer, tot_iter, args
         if i_iter == 0:
             gs.set_class_weights(criterion.class_weights)        # (new weights after a relabelling round, :527-530)
         gs.optimizer.lr = lr
+        if (gs.depth is None) != (depths is None):
+            raise RuntimeError('mspl_amd.script.train: the graphed step of this model was captured %s a depth batch and is now called '
+                               '%s one; a captured step cannot change its inputs (train a fresh model object)'
+                               % (('without', 'with') if gs.depth is None else ('with', 'without')))
         if tuple(images.shape) == tuple(gs.images.shape):
-            gs(images, labels)
+            gs(images, labels, depths)
         else:                                                    # the loader has no drop_last: same FlatAdam, same meters, eager
-            training.train_step(model, images, labels, gs.cw, gs.optimizer, None, ce_scale=gs.ce_scale, meters=meters, add_loss=add_loss)
-    return images, labels, None
+            training.train_step(model, images, labels, gs.cw, gs.optimizer, None, ce_scale=gs.ce_scale, meters=meters, add_loss=add_loss,
+                                depth=depths)
+    return images, labels, depths
 
 
 def _train_restated(trainloader, model, criterion, device, optimizer, tot_iter, args, add_loss, meters):
@@ -231,13 +244,14 @@ def _train(namespace, trainloader, model, criterion, device, interp, optimizer, 
 def train(trainloader, model, criterion, device, interp, optimizer, tot_iter, round_idx, epoch_idx, args, logger, metric,
           class_encoding, writer_idx, class_weights=None, writer=None, add_loss=None):
     """uest_seg_multi_os.py:958-1089 with its own signature; returns writer_idx + 1.  `interp` is ignored (:986), `round_idx`,
-    `epoch_idx`, `logger`, `metric` and `class_weights` are accepted and unused, as there.  With the shipped settings (espdnetue, no
-    depth, --use-uncertainty, a model in eval() mode, the drop-in UncertaintyWeightedSegmentationLoss, one-group torch.optim.Adam)
+    `epoch_idx`, `logger`, `metric` and `class_weights` are accepted and unused, as there.  With the shipped settings (espdnetue, with
+    or without `args.use_depth` -- batch[2] is then the depth batch --, --use-uncertainty, a model in eval() mode, the drop-in
+    UncertaintyWeightedSegmentationLoss, one-group torch.optim.Adam)
     the steps run on training.GraphedTrainStep with `args.train_lanes` (default 2) micro-batch lanes and the meters are taken
     inside the loss kernel; the caller's Adam then never steps and holds no state.  `add_loss` (--use-nid) may be None or the drop-in
     NIDLoss with label_bin equal to the model's class count: its term is then taken from the low-resolution main head inside the
     same graph (NIDLoss.at_heads), on ONE lane whatever `args.train_lanes` says (the NID histogram couples the images of a batch).
-    Everything else runs the reference body on the drop-in modules."""
+    Everything else -- RGB-D batches together with an additional loss among it -- runs the reference body on the drop-in modules."""
     return _train(None, trainloader, model, criterion, device, interp, optimizer, tot_iter, round_idx, epoch_idx, args, logger, metric,
                   class_encoding, writer_idx, class_weights, writer, add_loss)
 

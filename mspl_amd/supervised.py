@@ -305,4 +305,7 @@ class GraphedSupervisedStep(GraphedStep):
         self.criterion = criterion
 
     def __call__(self, inputs, target, depth=None):
+        if (depth is None) != (self.depth is None):
+            raise RuntimeError('GraphedSupervisedStep: captured %s a depth batch, called %s one (the graph is fixed at construction)'
+                               % (('without', 'with') if self.depth is None else ('with', 'without')))
         return super().__call__(inputs, target, depth)

@@ -102,7 +102,7 @@ def _additional_loss(add_loss, images, main, pred, meters):
     return loss2
 
 
-def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=False, meters=None, add_loss=None):
+def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=False, meters=None, add_loss=None, depth=None):
     """model forward + uest loss (uest_seg_multi_os.py:1010-1023) on device class weights `cw`.  A model that exposes its decoder
     outputs (`forward_lowres`: main at H/2, auxiliary at H/4) gets the loss taken at head resolution -- the up-sampling of
     espdnet_ue.py:301-302 happens inside the loss kernel (ag.uw_loss_heads), same value and gradients; any other model is called as
@@ -111,14 +111,16 @@ def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=F
 
     add_loss: the additional loss of train(..., add_loss=...) (:1027-1030), added to the returned loss; a losses.NIDLoss is taken from
     the low-resolution main head too (NIDLoss.at_heads) where the plan of its kernels covers the shape.  It sees all images of a
-    batch at one pixel position together, so it goes with out_scale = 1 only (no micro-batch lanes)."""
+    batch at one pixel position together, so it goes with out_scale = 1 only (no micro-batch lanes).
+
+    depth: the (N,1,H,W) depth batch of an RGB-D model (model(x, x_d), espdnet_ue.py:186-270), or None."""
     if add_loss is not None and out_scale != 1.0:
         raise RuntimeError('mspl_amd.training.forward_loss: an additional loss couples the images of a batch; it cannot be split '
                            'into micro-batch lanes (out_scale = %g)' % out_scale)
     lowres = getattr(model, 'forward_lowres', None) if _LOSS_AT_HEADS else None
     main = None
     if lowres is not None:
-        main, aux = lowres(images)
+        main, aux = lowres(images, depth) if depth is not None else lowres(images)
         if aux is None:
             raise RuntimeError('mspl_amd.training.forward_loss: %s returns one head; the uest loss needs the auxiliary head of a '
                                'two-head model' % type(model).__name__)
@@ -130,7 +132,7 @@ def forward_loss(model, images, labels, cw, ce_scale=20.0, out_scale=1.0, root=F
         size = tuple(images.shape[2:])
         pred, aux = ag.bilinear(main, size), ag.bilinear(aux, size)
     else:
-        pred, aux = model(images)
+        pred, aux = model(images, depth) if depth is not None else model(images)
     loss = ag.uw_loss(pred, aux, labels, cw, ce_scale, out_scale, root)
     if meters is not None:      # the three-step form: the existing area kernel on the full-size main head, loss * B added on the device
         meters.add(pred, labels, loss, images.shape[0] / out_scale)
@@ -188,13 +190,13 @@ def adjust_learning_rate(optimizer, i_iter, tot_iter, base_lr, power=0.0):
 
 
 def train_step(model, images, labels, class_weights, optimizer=None, ignore_idx=None, lr=5e-4, weight_decay=5e-4,
-               ce_scale=20.0, meters=None, add_loss=None):
+               ce_scale=20.0, meters=None, add_loss=None, depth=None):
     """One optimisation step; returns (loss tensor, optimizer).  Pass optimizer=None on the first call: it is built
     after the first backward (which reveals the gradient-bearing parameters).  meters: a TrainMeters the step is added to.
-    add_loss: the additional loss of train(..., add_loss=...), see forward_loss."""
+    add_loss: the additional loss of train(..., add_loss=...), see forward_loss.  depth: the depth batch of an RGB-D model."""
     def loss_fn():
         return forward_loss(model, images, labels, _device_class_weights(class_weights, images.device, ignore_idx), ce_scale,
-                            meters=meters, add_loss=add_loss), None
+                            meters=meters, add_loss=add_loss, depth=depth), None
 
     loss, _, optimizer = run_step(model, optimizer, images.shape[0], loss_fn,
                                   lambda: FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay), meters)
@@ -236,8 +238,10 @@ class GraphedTrainStep(GraphedStep):
     it has cross terms between the images of a batch, and micro-batch lanes would compute another loss."""
 
     def __init__(self, model, images, labels, class_weights, ignore_idx=None, lr=5e-4, weight_decay=5e-4, ce_scale=20.0, lanes=1,
-                 meters=None, consume_first_batch=True, add_loss=None):
-        """meters: a TrainMeters captured inside the graph(s) -- every lane adds into the same buffers; it is reset when the
+                 meters=None, consume_first_batch=True, add_loss=None, depth=None):
+        """depth: the (N,1,H,W) depth batch of an RGB-D model: a static buffer after `labels`, sliced per lane like the images.  A
+        step captured with depth must be called with depth and one captured without must not (the graph is one or the other).
+        meters: a TrainMeters captured inside the graph(s) -- every lane adds into the same buffers; it is reset when the
         constructor returns.  consume_first_batch=False: the construction batch only shapes the capture -- the parameters are put
         back to their values on entry, both Adam moments, the step count and the meters are zeroed, so the first call is step 1 (a
         training loop applies each batch exactly once; the default applies the construction batch twice: an eager step, then the
@@ -247,17 +251,23 @@ class GraphedTrainStep(GraphedStep):
         self.ce_scale = ce_scale
         self.lanes = lanes if (lanes > 1 and images.shape[0] % lanes == 0 and add_loss is None) else 1
         # (the eager step gets the caller's class weights and no meters; the capture reads this object's own `cw`)
-        self._build([('images', images), ('labels', labels.to(torch.int64))],
+        self._build([('images', images), ('labels', labels.to(torch.int64)), ('depth', depth)],
                     lambda: train_step(model, self.images, self.labels, class_weights, None, ignore_idx, lr, weight_decay, ce_scale,
-                                       add_loss=add_loss)[1],
+                                       add_loss=add_loss, depth=self.depth)[1],
                     consume_first_batch)
 
-    def _lane_loss(self, images, labels, out_scale=1.0):
+    def _lane_loss(self, images, labels, out_scale=1.0, depth=None):
         return forward_loss(self.model, images, labels, self.cw, self.ce_scale, out_scale=out_scale, root=True, meters=self.meters,
-                            add_loss=self.add_loss)
+                            add_loss=self.add_loss, depth=depth)
 
     def _loss(self):
-        return self._lane_loss(self.images, self.labels), None
+        return self._lane_loss(self.images, self.labels, depth=self.depth), None
+
+    def __call__(self, images, labels, depth=None):
+        if (depth is None) != (self.depth is None):
+            raise RuntimeError('GraphedTrainStep: captured %s a depth batch, called %s one (the graph is fixed at construction)'
+                               % (('without', 'with') if self.depth is None else ('with', 'without')))
+        return super().__call__(images, labels, depth)
 
     def _capture(self):
         if self.lanes == 1:
@@ -286,7 +296,8 @@ class GraphedTrainStep(GraphedStep):
                 g = torch.cuda.CUDAGraph()
                 with layers.graph_capture(g, stream=st):
                     with torch.enable_grad(), ag.grad_sinks(), tr.active(refresh=False):
-                        loss = self._lane_loss(self.images[i * b:(i + 1) * b], self.labels[i * b:(i + 1) * b], 1.0 / self.lanes)
+                        loss = self._lane_loss(self.images[i * b:(i + 1) * b], self.labels[i * b:(i + 1) * b], 1.0 / self.lanes,
+                                               None if self.depth is None else self.depth[i * b:(i + 1) * b])
                         loss.backward()
                 self.lane_graphs.append(g)
                 self.lane_losses.append(loss)
