@@ -17,6 +17,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "pyr_geom.hpp"
 
 namespace mspl {
 
@@ -33,10 +34,6 @@ struct PdbGeom {
     float* gx[PDB_MAXB];              // (N, P, h, w)
 };
 
-// ATen's adaptive pooling window of output o: [floor(o * I / O), ceil((o + 1) * I / O))
-__device__ __forceinline__ int pdb_s(int o, int I, int O) { return (int)(((unsigned)o * (unsigned)I) / (unsigned)O); }
-__device__ __forceinline__ int pdb_e(int o, int I, int O) { return (int)((((unsigned)(o + 1)) * (unsigned)I + O - 1) / (unsigned)O); }
-
 __global__ __launch_bounds__(256) void pyr_down_mid_bwd_kernel(PdbGeom g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int plane = blockIdx.x, bi = blockIdx.y, band = blockIdx.z;
@@ -50,8 +47,8 @@ __global__ __launch_bounds__(256) void pyr_down_mid_bwd_kernel(PdbGeom g) {
     // were 62 KB: two workgroups per CU; a quarter of it is nine).
     const int r0 = band * hs / g.bands, r1 = (band + 1) * hs / g.bands;
     const int y0 = band * h / g.bands, y1 = (band + 1) * h / g.bands;
-    const int ia = (int)(((unsigned)y0 * (unsigned)hs) / (unsigned)h);
-    const int ib = y1 > y0 ? min(hs - 1, (int)(((unsigned)(y1 - 1) * (unsigned)hs) / (unsigned)h) + 2) : ia - 1;
+    const int ia = pyr_bin_s(y0, hs, h);
+    const int ib = y1 > y0 ? min(hs - 1, pyr_bin_s(y1 - 1, hs, h) + 2) : ia - 1;
     const int lo = min(r0, ia - 1), hi = max(r1 - 1, ib + 1);            // actual rows of g_e held (-1 and hs are the zero halo)
     const int nge = min(hi - lo + 1, g.ger[bi]);                          // (the host sized ger / gpr from the same expressions)
     float* GE = smem;                                  // [nge][(ws + 2)], zero halo; local row = actual row - lo
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(256) void pyr_down_mid_bwd_kernel(PdbGeom g) {
         for (int k = 0; k < 3; ++k) {
             const int i = i0 + k;
             float rh = 0.f;
-            if (i < hs) { const int ys = pdb_s(i, h, hs), ye = pdb_e(i, h, hs); if (y >= ys && y < ye) rh = 1.0f / (float)(ye - ys); }
+            if (i < hs) { const int ys = pyr_bin_s(i, h, hs), ye = pyr_bin_e(i, h, hs); if (y >= ys && y < ye) rh = 1.0f / (float)(ye - ys); }
             RT[4 * r + 1 + k] = __float_as_int(rh);
         }
     }
@@ -139,7 +136,7 @@ __global__ __launch_bounds__(256) void pyr_down_mid_bwd_kernel(PdbGeom g) {
             const int j = j0 + k;
             rw[k] = 0.f;
             jc[k] = min(j, ws - 1);                      // (a window that does not exist reads a finite neighbour with weight 0)
-            if (j < ws) { const int xs = pdb_s(j, w, ws), xe = pdb_e(j, w, ws); if (x >= xs && x < xe) rw[k] = 1.0f / (float)(xe - xs); }
+            if (j < ws) { const int xs = pyr_bin_s(j, w, ws), xe = pyr_bin_e(j, w, ws); if (x >= xs && x < xe) rw[k] = 1.0f / (float)(xe - xs); }
         }
         for (int r = 0; r < y1 - y0; ++r) {             // uniform
             const int i0 = RT[4 * r];
@@ -194,8 +191,8 @@ extern "C" int mspl_pyr_down_mid_bwd(const float* const* g_e, const float* const
         for (int b = 0; b < bands; ++b) {               // the kernel's own expressions
             const int r0 = b * hs[i] / bands, r1 = (b + 1) * hs[i] / bands;
             const int y0 = b * h / bands, y1 = (b + 1) * h / bands;
-            const int ia = (int)(((unsigned)y0 * (unsigned)hs[i]) / (unsigned)h);
-            const int ib = y1 > y0 ? std::min(hs[i] - 1, (int)(((unsigned)(y1 - 1) * (unsigned)hs[i]) / (unsigned)h) + 2) : ia - 1;
+            const int ia = pyr_bin_s(y0, hs[i], h);
+            const int ib = y1 > y0 ? std::min(hs[i] - 1, pyr_bin_s(y1 - 1, hs[i], h) + 2) : ia - 1;
             ger = std::max(ger, std::max(r1 - 1, ib + 1) - std::min(r0, ia - 1) + 1);
             gpr = std::max(gpr, ib - ia + 1);
             rows_max = std::max(rows_max, y1 - y0);

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "pyr_geom.hpp"
 
 namespace mspl {
 
@@ -31,9 +32,6 @@ struct PrepGeom {
     unsigned xcd_per, total;                      // XCD-contiguous order (common.hpp): the bands of a plane overlap by their halo rows
 };
 
-__device__ __host__ __forceinline__ int pp_s(int o, int I, int O) { return (int)(((unsigned)o * (unsigned)I) / (unsigned)O); }
-__device__ __host__ __forceinline__ int pp_e(int o, int I, int O) { return (int)((((unsigned)(o + 1)) * (unsigned)I + O - 1) / (unsigned)O); }
-
 // Input rows [ylo, yhi) that band `band` of the S bands needs for all its branches (pooled rows ra-1 .. rb of each).
 __device__ __host__ __forceinline__ void pp_band_rows(const PrepGeom& g, int band, int& ylo, int& yhi) {
     ylo = g.h;  yhi = 0;
@@ -42,7 +40,7 @@ __device__ __host__ __forceinline__ void pp_band_rows(const PrepGeom& g, int ban
         const int ra = band * hs / g.S, rb = (band + 1) * hs / g.S;
         if (rb <= ra) continue;
         const int a = ra - 1 < 0 ? 0 : ra - 1, b = rb + 1 > hs ? hs : rb + 1;      // pooled rows [a, b)
-        const int lo = pp_s(a, g.h, hs), hi = pp_e(b - 1, g.h, hs);
+        const int lo = pyr_bin_s(a, g.h, hs), hi = pyr_bin_e(b - 1, g.h, hs);
         ylo = lo < ylo ? lo : ylo;  yhi = hi > yhi ? hi : yhi;
     }
 }
@@ -105,10 +103,10 @@ __global__ __launch_bounds__(256) void pyr_down_prep_kernel(const float* __restr
             const int nrow = rb > ra ? rb - ra + 2 : 0;
             for (int t = tid; t < ws + nrow; t += 256) {
                 int lo, hi;
-                if (t < ws) { lo = pp_s(t, g.w, ws); hi = pp_e(t, g.w, ws); }
+                if (t < ws) { lo = pyr_bin_s(t, g.w, ws); hi = pyr_bin_e(t, g.w, ws); }
                 else {
                     const int oy = ra - 1 + (t - ws);
-                    if (oy >= 0 && oy < hs) { lo = pp_s(oy, g.h, hs) - ylo; hi = pp_e(oy, g.h, hs) - ylo; } else { lo = 0; hi = 0; }
+                    if (oy >= 0 && oy < hs) { lo = pyr_bin_s(oy, g.h, hs) - ylo; hi = pyr_bin_e(oy, g.h, hs) - ylo; } else { lo = 0; hi = 0; }
                 }
                 XB[base + t] = lo | (hi << 16);
             }
@@ -290,7 +288,7 @@ __global__ __launch_bounds__(1024) void pyr_prep_stream_kernel(const float* __re
                 const int o = ob + gid;
                 const bool ok = o < hs;
                 const int oc = ok ? o : hs - 1;
-                const int y0 = pp_s(oc, g.h, hs), y1 = pp_e(oc, g.h, hs);
+                const int y0 = pyr_bin_s(oc, g.h, hs), y1 = pyr_bin_e(oc, g.h, hs);
                 vecw r[PS_MAXWIN];
 #pragma unroll
                 for (int t = 0; t < PS_MAXWIN; ++t) {
@@ -317,7 +315,7 @@ __global__ __launch_bounds__(1024) void pyr_prep_stream_kernel(const float* __re
                 }
                 // (same wave: its LDS operations execute in order, the reads below see the writes above)
                 for (int ox = cl; ox < ws; ox += lprp) {
-                    const int x0 = pp_s(ox, w, ws), x1 = pp_e(ox, w, ws);
+                    const int x0 = pyr_bin_s(ox, w, ws), x1 = pyr_bin_e(ox, w, ws);
                     float b0 = 0.f, b1 = 0.f;
                     int xx = x0;
                     for (; xx + 1 < x1; xx += 2) { b0 += RB[xx]; b1 += RB[xx + 1]; }
@@ -454,15 +452,6 @@ extern "C" int64_t mspl_pyr_down_prep_lds_bytes(int32_t N, int32_t P, int32_t h,
     return (int64_t)prep_plan(g, (int64_t)N * P);
 }
 
-extern "C" int mspl_pyr_down_prep_train_fwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs,
-                                            const int32_t* ws, const float* const* stage_w, float* const* out, float* const* pooled,
-                                            void* stream);
-
-extern "C" int mspl_pyr_down_prep_fwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs,
-                                      const int32_t* ws, const float* const* stage_w, float* const* out, void* stream) {
-    return mspl_pyr_down_prep_train_fwd(x, N, P, h, w, nb, hs, ws, stage_w, out, nullptr, stream);
-}
-
 // The training forward: the same launch also writes the pooled maps p_i = adaptive_avg_pool2d(x, (hs_i, ws_i)) (pooled[i], or
 // pooled == NULL), which the depthwise convolutions' weight gradient needs.
 extern "C" int mspl_pyr_down_prep_train_fwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs,
@@ -471,25 +460,20 @@ extern "C" int mspl_pyr_down_prep_train_fwd(const float* x, int32_t N, int32_t P
     MSPL_REQUIRE(x && hs && ws && stage_w && out, MSPL_ERR_NULL_POINTER, "pyr_down_prep: null pointer");
     MSPL_REQUIRE(N > 0 && P > 0 && h > 0 && w > 0, MSPL_ERR_BAD_SHAPE, "pyr_down_prep: bad shape N=%d P=%d %dx%d", N, P, h, w);
     MSPL_REQUIRE(nb >= 1 && nb <= PP_MAXB, MSPL_ERR_UNSUPPORTED, "pyr_down_prep: %d branches (1..%d)", nb, PP_MAXB);
-    for (int i = 0; i < nb; ++i) {
-        MSPL_REQUIRE(hs[i] > 0 && ws[i] > 0 && hs[i] <= h && ws[i] <= w, MSPL_ERR_BAD_SHAPE,
-                     "pyr_down_prep: branch %d size %dx%d for a %dx%d map", i, hs[i], ws[i], h, w);
-        MSPL_REQUIRE(stage_w[i] && out[i], MSPL_ERR_NULL_POINTER, "pyr_down_prep: branch %d has a null pointer", i);
-    }
-    {
-        const int rc = mspl::prep_stream_try(x, N, P, h, w, nb, hs, ws, stage_w, out, pooled, (hipStream_t)stream);
-        if (rc <= 0) return rc;
-    }
-    PrepGeom g;
+    PrepGeom g;                                   // (the band form's; filled while the branches are checked)
     memset(&g, 0, sizeof(g));
     g.N = N; g.P = P; g.h = h; g.w = w; g.nb = nb;
-    const int64_t planes = (int64_t)N * P;
     for (int i = 0; i < nb; ++i) {
         MSPL_REQUIRE(hs[i] > 0 && ws[i] > 0 && hs[i] <= h && ws[i] <= w, MSPL_ERR_BAD_SHAPE,
                      "pyr_down_prep: branch %d size %dx%d for a %dx%d map", i, hs[i], ws[i], h, w);
         MSPL_REQUIRE(stage_w[i] && out[i], MSPL_ERR_NULL_POINTER, "pyr_down_prep: branch %d has a null pointer", i);
         g.hs[i] = hs[i]; g.ws[i] = ws[i]; g.wts[i] = stage_w[i]; g.out[i] = out[i]; g.pool[i] = pooled ? pooled[i] : nullptr;
     }
+    {
+        const int rc = mspl::prep_stream_try(x, N, P, h, w, nb, hs, ws, stage_w, out, pooled, (hipStream_t)stream);
+        if (rc <= 0) return rc;
+    }
+    const int64_t planes = (int64_t)N * P;
     const size_t lds = prep_plan(g, planes);
     static const int dbg_stop = MSPL_TUNE_INT("MSPL_PREP_STOP", 0);
     g.stop = dbg_stop;
@@ -500,4 +484,9 @@ extern "C" int mspl_pyr_down_prep_train_fwd(const float* x, int32_t N, int32_t P
     hipLaunchKernelGGL(pyr_down_prep_kernel, dim3(8u * g.xcd_per), dim3(256), lds, (hipStream_t)stream, x, g);
     MSPL_CHECK_LAUNCH("pyr_down_prep");
     return MSPL_OK;
+}
+
+extern "C" int mspl_pyr_down_prep_fwd(const float* x, int32_t N, int32_t P, int32_t h, int32_t w, int32_t nb, const int32_t* hs,
+                                      const int32_t* ws, const float* const* stage_w, float* const* out, void* stream) {
+    return mspl_pyr_down_prep_train_fwd(x, N, P, h, w, nb, hs, ws, stage_w, out, nullptr, stream);
 }

@@ -17,10 +17,10 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "pyr_geom.hpp"
 
 namespace mspl {
 
-constexpr int PYR_MAXB = 5;
 constexpr int PYR_HALO = 4;      // x-tile halo that covers every bilinear source of the up-sampled tiles
 
 struct PyrGeom {
@@ -44,8 +44,6 @@ struct PyrGeom {
     float* zcat;                        // training forward: (N, nb*P, h, w), the branch values BEFORE merge_layer.0 (torch.cat order), or null
 };
 
-__device__ __forceinline__ int ada_s(int o, int I, int O) { return (int)(((unsigned)o * (unsigned)I) / (unsigned)O); }
-__device__ __forceinline__ int ada_e(int o, int I, int O) { return (int)((((unsigned)(o + 1)) * (unsigned)I + O - 1) / (unsigned)O); }
 __device__ __forceinline__ int fdiv(int t, unsigned magic) { return (int)(((unsigned)t * magic) >> 24); }
 
 // Table layout of branch i inside LDS (float words; ints stored bit-cast):
@@ -76,7 +74,7 @@ __global__ __launch_bounds__(256) void pyrpool_fused_kernel(const float* __restr
         float* T = smem + g.toff[i];
         if (g.kind[i] == 0) {
             const int UH = g.UH[i], UW = g.UW[i];
-            const int u0 = ada_s(py_lo, g.hs[i], g.h) - 1, v0 = ada_s(px_lo, g.ws[i], g.w) - 1;
+            const int u0 = pyr_bin_s(py_lo, g.hs[i], g.h) - 1, v0 = pyr_bin_s(px_lo, g.ws[i], g.w) - 1;
             float* UR = T; float* UC = UR + 4 * UH; float* WR = UC + 4 * UW; float* WC = WR + 2 * BH;
             for (int t = tid; t < UH + UW + BH + BW2; t += 256) {
                 if (t < UH) {
@@ -94,12 +92,12 @@ __global__ __launch_bounds__(256) void pyrpool_fused_kernel(const float* __restr
                 } else if (t < UH + UW + BH) {
                     const int r = t - UH - UW, py = y0 - 1 + r;
                     int first = 0, cnt = 0;
-                    if (py >= 0 && py < g.h) { const int us = ada_s(py, g.hs[i], g.h); first = us - 1 - u0; cnt = ada_e(py, g.hs[i], g.h) - us; }
+                    if (py >= 0 && py < g.h) { const int us = pyr_bin_s(py, g.hs[i], g.h); first = us - 1 - u0; cnt = pyr_bin_e(py, g.hs[i], g.h) - us; }
                     WR[2 * r] = __int_as_float(first * UW); WR[2 * r + 1] = __int_as_float(cnt);
                 } else {
                     const int q = t - UH - UW - BH, px = x0 - 1 + q;
                     int first = 0, cnt = 0;
-                    if (px >= 0 && px < g.w) { const int vs = ada_s(px, g.ws[i], g.w); first = vs - 1 - v0; cnt = ada_e(px, g.ws[i], g.w) - vs; }
+                    if (px >= 0 && px < g.w) { const int vs = pyr_bin_s(px, g.ws[i], g.w); first = vs - 1 - v0; cnt = pyr_bin_e(px, g.ws[i], g.w) - vs; }
                     WC[2 * q] = __int_as_float(first); WC[2 * q + 1] = __int_as_float(cnt);
                 }
             }
@@ -367,19 +365,6 @@ __global__ __launch_bounds__(256) void pyrpool_fused_kernel(const float* __restr
     }
 }
 
-int pyrpool_sep_try(const float* x, int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws,
-                    const float* const* stage_w, const float* const* down_e, const float* br_scale,
-                    const float* br_shift, const float* br_alpha, const float* merge_w, const Epi& e, float* out,
-                    hipStream_t stream, unsigned launch_flags);       // pyrpool_sep.hip
-int pyrpool_stream_try(const float* x, int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws,
-                       const float* const* stage_w, const float* const* down_e, const float* br_scale,
-                       const float* br_shift, const float* br_alpha, const float* merge_w, const Epi& e, float* out,
-                       hipStream_t stream, float* zcat = nullptr, const float* tab = nullptr);    // pyrpool_stream.hip
-int pyrpool_stream_tables_build(int h, int w, int nb, const int32_t* hs, const int32_t* ws, float* tab, int64_t bytes,
-                                hipStream_t stream);
-int64_t pyrpool_stream_tables_bytes(int h, int w, int nb, const int32_t* hs, const int32_t* ws);
-void pyrpool_stream_plan(int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws, int32_t* out);
-
 }  // namespace mspl
 
 using namespace mspl;
@@ -396,16 +381,17 @@ static int pyrpool_fused_launch(const float* x, int32_t N, int32_t P, int32_t h,
     MSPL_REQUIRE(N > 0 && P > 0 && h > 0 && w > 0, MSPL_ERR_BAD_SHAPE, "pyrpool_fused: bad shape N=%d P=%d %dx%d", N, P, h, w);
     MSPL_REQUIRE(nb >= 1 && nb <= PYR_MAXB, MSPL_ERR_UNSUPPORTED, "pyrpool_fused: %d branches (1..%d)", nb, PYR_MAXB);
     if (int rc = check_epi(ep, P, "pyrpool_fused", zcat != nullptr)) return rc;
+    const PyrBranches br = pyr_classify(h, w, nb, hs, ws);
     if (!dry) {   // register-streaming form first, then the LDS-tiled stencil form; shapes they do not cover fall through to the table-driven kernel
         static const int force_tables = MSPL_TUNE_INT("MSPL_PYR_TABLES", 0);
         if (!force_tables) {
+            const PyrFwdArgs a = {x, N, P, h, w, nb, hs, ws, stage_w, down_e, br_scale, br_shift, br_alpha, merge_w,
+                                  make_epi(ep, P, h * w), out, zcat, tab, (hipStream_t)stream, br};
             // (the training forward -- zcat wanted -- exists in the streaming and in the table form)
-            const int rc3 = pyrpool_stream_try(x, N, P, h, w, nb, hs, ws, stage_w, down_e, br_scale, br_shift, br_alpha, merge_w,
-                                               make_epi(ep, P, h * w), out, (hipStream_t)stream, zcat, tab);
+            const int rc3 = pyrpool_stream_try(a);
             if (rc3 <= 0) return rc3;
             if (!zcat) {
-                const int rc = pyrpool_sep_try(x, N, P, h, w, nb, hs, ws, stage_w, down_e, br_scale, br_shift, br_alpha, merge_w,
-                                               make_epi(ep, P, h * w), out, (hipStream_t)stream, epi_flags(ep));
+                const int rc = pyrpool_sep_try(a);
                 if (rc <= 0) return rc;
             }
         }
@@ -426,27 +412,22 @@ static int pyrpool_fused_launch(const float* x, int32_t N, int32_t P, int32_t h,
         MSPL_REQUIRE(hs[i] > 0 && ws[i] > 0, MSPL_ERR_BAD_SHAPE, "pyrpool_fused: branch %d size %dx%d", i, hs[i], ws[i]);
         g.hs[i] = hs[i]; g.ws[i] = ws[i];
         g.stage_w[i] = dry ? nullptr : stage_w[i]; g.down_e[i] = dry ? nullptr : down_e[i];
-        if (hs[i] == h && ws[i] == w) {
-            g.kind[i] = 1;
-            MSPL_REQUIRE(dry || stage_w[i], MSPL_ERR_NULL_POINTER, "pyrpool_fused: branch %d needs stage weights", i);
-        } else if (hs[i] >= h && ws[i] >= w) {
-            g.kind[i] = 0;
-            MSPL_REQUIRE(dry || stage_w[i], MSPL_ERR_NULL_POINTER, "pyrpool_fused: branch %d needs stage weights", i);
+        g.kind[i] = br.kind[i];
+        if (br.kind[i] == PYR_MIXED) {
+            set_error("pyrpool_fused: branch %d mixes up- and down-sampling (%dx%d vs %dx%d)", i, hs[i], ws[i], h, w);
+            return MSPL_ERR_UNSUPPORTED;
+        }
+        if (br.kind[i] == PYR_DOWN) MSPL_REQUIRE(dry || down_e[i], MSPL_ERR_NULL_POINTER, "pyrpool_fused: branch %d needs its low-resolution map", i);
+        else MSPL_REQUIRE(dry || stage_w[i], MSPL_ERR_NULL_POINTER, "pyrpool_fused: branch %d needs stage weights", i);
+        if (br.kind[i] != PYR_SAME) { g.sh[i] = br.sh[i]; g.sw[i] = br.sw[i]; }
+        if (br.kind[i] == PYR_UP) {
             // windows of an up-sampled branch must stay small (x-tile halo of 4 covers scales in [1, 4])
             MSPL_REQUIRE(hs[i] <= 4 * h && ws[i] <= 4 * w, MSPL_ERR_UNSUPPORTED, "pyrpool_fused: up-scale beyond 4x");
-            g.sh[i] = bilinear_scale(h, hs[i]); g.sw[i] = bilinear_scale(w, ws[i]);
             g.UH[i] = (int)(((int64_t)(g.TH + 2) * hs[i] + h - 1) / h) + 4;
             g.UW[i] = (int)(((int64_t)(g.TW + 2) * ws[i] + w - 1) / w) + 4;
             g.uoff[i] = off;
             off += g.UH[i] * g.UW[i];
             off = (off + 3) & ~3;
-        } else if (hs[i] <= h && ws[i] <= w) {
-            g.kind[i] = 2;
-            MSPL_REQUIRE(dry || down_e[i], MSPL_ERR_NULL_POINTER, "pyrpool_fused: branch %d needs its low-resolution map", i);
-            g.sh[i] = bilinear_scale(hs[i], h); g.sw[i] = bilinear_scale(ws[i], w);
-        } else {
-            set_error("pyrpool_fused: branch %d mixes up- and down-sampling (%dx%d vs %dx%d)", i, hs[i], ws[i], h, w);
-            return MSPL_ERR_UNSUPPORTED;
         }
     }
     auto magic = [](int d) { return (unsigned)(((1u << 24) + (unsigned)d - 1) / (unsigned)d); };

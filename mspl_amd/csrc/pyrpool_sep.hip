@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "pyr_geom.hpp"
 
 namespace mspl {
 
@@ -50,9 +51,6 @@ __host__ __device__ constexpr int p2_ks(int T) { return T <= 3 ? 4 : 8; }
 __host__ __device__ constexpr int p2_ts(int T) { return 3 * p2_ks(T); }
 // C tables: floats per strip = 4 rows + 4 pad, so that the strips of a wave land on distinct LDS banks
 __host__ __device__ constexpr int p2_cs(int T) { return 4 * p2_ts(T) + 4; }
-
-__device__ __forceinline__ int p2_ada_s(int o, int I, int O) { return (int)(((unsigned)o * (unsigned)I) / (unsigned)O); }
-__device__ __forceinline__ int p2_ada_e(int o, int I, int O) { return (int)((((unsigned)(o + 1)) * (unsigned)I + O - 1) / (unsigned)O); }
 
 template <int T>
 __device__ __forceinline__ void p2_load_row(const float* __restrict__ p, float (&v)[5]) {
@@ -98,7 +96,8 @@ __device__ __forceinline__ void up_branch_strip(const float (&xp)[5][8], const f
     }
 }
 
-// Channel-independent stencil table of one up branch: rows [pos][ky][KS]; thread t handles (pos, k).
+// Channel-independent stencil table of one up branch: rows [pos][ky][KS]; thread t handles (pos, k).  The body is the twin of
+// p3_coeffs (pyr_geom.hpp): the same values, kept apart because merging them changes this kernel's register allocation.
 template <int T>
 __device__ __forceinline__ void p2_fill_up_tables(float* A, float* G, int BH, int BW, int y0, int x0, int h, int w,
                                                   int hs, int ws, float sh, float sw, int tid) {
@@ -113,7 +112,7 @@ __device__ __forceinline__ void p2_fill_up_tables(float* A, float* G, int BH, in
         const float sc = isrow ? sh : sw;
         float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
         if (p >= 0 && p < I) {
-            const int us = p2_ada_s(p, S, I), ue = p2_ada_e(p, S, I);
+            const int us = pyr_bin_s(p, S, I), ue = pyr_bin_e(p, S, I);
             const float inv = 1.0f / (float)(ue - us);
             for (int uu = us; uu < ue; ++uu) {
                 const int v = uu + k - 1;
@@ -451,40 +450,15 @@ __global__ __launch_bounds__(256, 3) void pyrpool_sep_kernel(const float* __rest
     }
 }
 
-// Host twin of bilinear_src's index part (same fp32 operations; -ffp-contract=off).
-static void host_bilinear_idx(float scale, int dst, int in_size, int& i0, int& i1) {
-    const float real = scale * (float)dst;
-    int idx = (int)floorf(real);
-    if (idx > in_size - 1) idx = in_size - 1;
-    i0 = idx;
-    i1 = idx + ((idx < in_size - 1) ? 1 : 0);
-}
-
-// Smallest R such that every source of output p lies in [p-R, p+R] (one dimension); large when unsupported.
-static int stencil_radius(int I, int S) {
-    const float sc = bilinear_scale(I, S);
-    int R = 0;
-    for (int p = 0; p < I; ++p) {
-        const int us = (int)(((int64_t)p * S) / I), ue = (int)((((int64_t)p + 1) * S + I - 1) / I);
-        for (int v = std::max(us - 1, 0); v <= std::min(ue, S - 1); ++v) {
-            int a, b;
-            host_bilinear_idx(sc, v, I, a, b);
-            R = std::max(R, std::max(p - a, b - p));
-        }
-    }
-    return R;
-}
-
 // Returns MSPL_OK when launched, 1 when the shape is left to the table-driven kernel, < 0 on error.
-int pyrpool_sep_try(const float* x, int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws,
-                    const float* const* stage_w, const float* const* down_e, const float* br_scale,
-                    const float* br_shift, const float* br_alpha, const float* merge_w, const Epi& e, float* out,
-                    hipStream_t stream, unsigned launch_flags) {
+int pyrpool_sep_try(const PyrFwdArgs& a) {
+    const Epi& e = a.e;
+    const int N = a.N, P = a.P, h = a.h, w = a.w, nb = a.nb;
     if (e.pre_add || e.residual || e.reinf_r || e.gate) return 1;    // only the scale/shift/PReLU epilogue
     Pyr2Geom g;
     memset(&g, 0, sizeof(g));
     g.N = N; g.P = P; g.h = h; g.w = w; g.nb = nb;
-    g.br_scale = br_scale; g.br_shift = br_shift; g.br_alpha = br_alpha; g.merge_w = merge_w;
+    g.br_scale = a.br_scale; g.br_shift = a.br_shift; g.br_alpha = a.br_alpha; g.merge_w = a.merge_w;
     g.TW = w >= 32 ? 32 : ((w + 3) & ~3);
     g.NS = (g.TW + 2 + 3) / 4;
     g.BW = 4 * g.NS;
@@ -502,35 +476,27 @@ int pyrpool_sep_try(const float* x, int N, int P, int h, int w, int nb, const in
     int off = (g.TH + 6) * g.XW;
     int taps[2] = {3, 3}, nup = 0, nE = 0;
     for (int i = 0; i < nb; ++i) {
-        if (hs[i] <= 0 || ws[i] <= 0) return 1;
-        g.hs[i] = hs[i]; g.ws[i] = ws[i];
-        g.stage_w[i] = stage_w[i]; g.down_e[i] = down_e[i];
-        if (hs[i] == h && ws[i] == w) {
-            g.kind[i] = 1;
-            if (!stage_w[i]) return 1;
-        } else if (hs[i] >= h && ws[i] >= w) {
-            g.kind[i] = 0;
-            if (!stage_w[i] || nup >= 2) return 1;
-            const int R = std::max(stencil_radius(h, hs[i]), stencil_radius(w, ws[i]));
-            if (R > 2) return 1;
-            const int T = R <= 1 ? 3 : 5;
+        const int kind = a.br.kind[i];
+        if (kind == PYR_MIXED) return 1;
+        g.hs[i] = a.hs[i]; g.ws[i] = a.ws[i];
+        g.stage_w[i] = a.stage_w[i]; g.down_e[i] = a.down_e[i];
+        g.kind[i] = kind;
+        if (kind == PYR_DOWN ? !a.down_e[i] : !a.stage_w[i]) return 1;
+        if (kind != PYR_SAME) { g.sh[i] = a.br.sh[i]; g.sw[i] = a.br.sw[i]; }
+        if (kind == PYR_UP) {
+            const int T = a.br.taps[i];
+            if (nup >= 2 || T == 0) return 1;                 // two stencil branches of at most 5 taps
             taps[nup++] = T;
             g.taps[i] = T;
-            g.sh[i] = bilinear_scale(h, hs[i]); g.sw[i] = bilinear_scale(w, ws[i]);
             g.aoff[i] = off;  off += BH * p2_ts(T);
             g.goff[i] = off;  off += g.BW * p2_ts(T);
             g.coff[i] = off;  off += g.NS * p2_cs(T);
-        } else if (hs[i] <= h && ws[i] <= w) {
-            g.kind[i] = 2;
-            if (!down_e[i]) return 1;
-            g.sh[i] = bilinear_scale(hs[i], h); g.sw[i] = bilinear_scale(ws[i], w);
-            g.EH[i] = std::min(hs[i], (int)floorf((float)(g.TH + 1) * g.sh[i]) + 3);
-            g.EW[i] = std::min(ws[i], (int)floorf((float)(g.BW - 1) * g.sw[i]) + 3);
+        } else if (kind == PYR_DOWN) {
+            g.EH[i] = std::min(g.hs[i], (int)floorf((float)(g.TH + 1) * g.sh[i]) + 3);
+            g.EW[i] = std::min(g.ws[i], (int)floorf((float)(g.BW - 1) * g.sw[i]) + 3);
             g.doff[i] = off;  off += 4 * BH + 20 * g.NS;
             g.eoff[i] = off;  off += (g.EH[i] * g.EW[i] + 3) & ~3;
             g.epre[i] = nE;   nE += g.EH[i] * g.EW[i];
-        } else {
-            return 1;
         }
     }
     if (nE > 512) return 1;
@@ -542,7 +508,7 @@ int pyrpool_sep_try(const float* x, int N, int P, int h, int w, int nb, const in
     if (lds > 64 * 1024) return 1;
     // planes per workgroup (each workgroup walks them with the next plane's loads in flight): as many as keep >= 2048 workgroups
     // for a lone pass; with MSPL_LAUNCH_THROUGHPUT 512 are enough -- fewer, longer workgroups (+2.5 % images/s with three passes in flight)
-    const int64_t min_blocks = (launch_flags & MSPL_LAUNCH_THROUGHPUT) ? 512 : 2048;
+    const int64_t min_blocks = (e.flags & MSPL_LAUNCH_THROUGHPUT) ? 512 : 2048;
     int cpb = 1;
     while (cpb * 2 <= P && P % (cpb * 2) == 0 && (int64_t)N * (P / (cpb * 2)) * g.tiles_y * g.tiles_x >= min_blocks) cpb *= 2;
     static const int dbg_cpb = MSPL_TUNE_INT("MSPL_PYR_CPB", 0);
@@ -554,11 +520,8 @@ int pyrpool_sep_try(const float* x, int N, int P, int h, int w, int nb, const in
     if (blocks >= (1ll << 31)) return 1;
     g.total = (unsigned)blocks; g.xcd_per = xcd_per(blocks);
     const dim3 grid(8u * g.xcd_per), blk(256);
-#define MSPL_P2_LAUNCH(A, B) hipLaunchKernelGGL((pyrpool_sep_kernel<A, B>), grid, blk, lds, stream, x, e.scale, e.shift, e.alpha, e.ctot, e.coff, g, out)
-    if (taps[0] == 3 && taps[1] == 3) MSPL_P2_LAUNCH(3, 3);
-    else if (taps[0] == 3) MSPL_P2_LAUNCH(3, 5);
-    else if (taps[1] == 3) MSPL_P2_LAUNCH(5, 3);
-    else MSPL_P2_LAUNCH(5, 5);
+#define MSPL_P2_LAUNCH(A, B) hipLaunchKernelGGL((pyrpool_sep_kernel<A, B>), grid, blk, lds, a.stream, a.x, e.scale, e.shift, e.alpha, e.ctot, e.coff, g, a.out)
+    MSPL_PYR_TAP_DISPATCH(taps[0], taps[1], MSPL_P2_LAUNCH);
 #undef MSPL_P2_LAUNCH
     MSPL_CHECK_LAUNCH("pyrpool_fused(stencil form)");
     return MSPL_OK;

@@ -25,7 +25,7 @@
 #include <unordered_map>
 
 #include "common.hpp"
-#include "pyr_stencil.hpp"
+#include "pyr_geom.hpp"
 
 namespace mspl {
 
@@ -486,25 +486,16 @@ struct P3Shape {
     bool ok;
     int T0, T1, PXL, ncb, CBW;
 };
-static P3Shape p3_shape(int h, int w, int nb, const int32_t* hs, const int32_t* ws) {
+static P3Shape p3_shape(int h, int w, const PyrBranches& br) {
     P3Shape s;
     memset(&s, 0, sizeof(s));
     static const int off = (MSPL_TUNE_INT("MSPL_PYR_STREAM", 1) == 0);
     // maps narrower than ~half a wave leave most lanes idle: the LDS-tiled form is faster there (18x30: 12 vs 17 us)
     static const int min_w = MSPL_TUNE_INT("MSPL_PYR_STREAM_MINW", 40);
-    if (off || nb != 5 || w < min_w || h <= 0) return s;
-    // branch pattern: up, up, same, down, down (strictly)
-    for (int i = 0; i < 5; ++i) if (hs[i] <= 0 || ws[i] <= 0) return s;
-    if (!(hs[0] > h && ws[0] > w && hs[1] > h && ws[1] > w)) return s;
-    if (!(hs[2] == h && ws[2] == w)) return s;
-    if (!(hs[3] <= h && ws[3] <= w && hs[4] <= h && ws[4] <= w && (hs[3] < h || ws[3] < w) && (hs[4] < h || ws[4] < w))) return s;
-    int taps[2];
-    for (int i = 0; i < 2; ++i) {
-        const int R = std::max(p3_stencil_radius(h, hs[i]), p3_stencil_radius(w, ws[i]));
-        if (R > 2) return s;
-        taps[i] = R <= 1 ? 3 : 5;
-    }
-    s.T0 = taps[0]; s.T1 = taps[1];
+    if (off || br.nb != 5 || w < min_w || h <= 0) return s;
+    // branch pattern: up, up, same, down, down (strictly), both up branches stencils of at most 5 taps
+    if (!br.standard || br.taps[0] == 0 || br.taps[1] == 0) return s;
+    s.T0 = br.taps[0]; s.T1 = br.taps[1];
     s.PXL = w <= 62 ? 1 : 2;
     if (s.PXL == 2 && (w & 1)) return s;                   // 8-byte stores and x row loads
     s.CBW = 62 * s.PXL;
@@ -519,11 +510,11 @@ struct P3Plan {
     int seg_tab, nseg_tab, seg_ik, nseg_ik;                // rows per segment and segments per plane: tables from memory / in-kernel tables
     int64_t waves_tab, waves_ik;
 };
-static P3Plan p3_plan(int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws) {
+static P3Plan p3_plan(int N, int P, int h, int w, const PyrBranches& br) {
     P3Plan p;
     memset(&p, 0, sizeof(p));
     if (N <= 0 || P <= 0 || ((int64_t)N * P) % 4 != 0) return p;
-    p.s = p3_shape(h, w, nb, hs, ws);
+    p.s = p3_shape(h, w, br);
     if (!p.s.ok) return p;
     const int64_t cols = (int64_t)N * P * p.s.ncb;         // waves per row segment
     static const int dbg_seg = MSPL_TUNE_INT("MSPL_PYR_SEG", 0);
@@ -548,13 +539,13 @@ static P3Plan p3_plan(int N, int P, int h, int w, int nb, const int32_t* hs, con
 
 static size_t p3_table_floats(const P3Shape& s, int h) { return (size_t)2 * (h + 2) * 24 + (size_t)30 * (s.ncb * 62 + 2) * s.PXL; }
 
-static void p3_fill_geom(Pyr3Geom& g, const P3Shape& s, int N, int P, int h, int w, const int32_t* hs, const int32_t* ws) {
+static void p3_fill_geom(Pyr3Geom& g, const P3Shape& s, int N, int P, int h, int w, const int32_t* hs, const int32_t* ws,
+                         const PyrBranches& br) {
     memset(&g, 0, sizeof(g));
     g.N = N; g.P = P; g.h = h; g.w = w;
     for (int i = 0; i < 5; ++i) {
         g.hs[i] = hs[i]; g.ws[i] = ws[i];
-        if (i < 2) { g.sh[i] = bilinear_scale(h, hs[i]); g.sw[i] = bilinear_scale(w, ws[i]); }
-        if (i > 2) { g.sh[i] = bilinear_scale(hs[i], h); g.sw[i] = bilinear_scale(ws[i], w); }
+        if (i != 2) { g.sh[i] = br.sh[i]; g.sw[i] = br.sw[i]; }
     }
     g.CBW = s.CBW;
     g.ncb = s.ncb;
@@ -578,27 +569,19 @@ static std::unordered_map<const void*, P3TabKey>& p3_tab_registry() {
 
 int pyrpool_stream_tables_build(int h, int w, int nb, const int32_t* hs, const int32_t* ws, float* tab, int64_t bytes,
                                 hipStream_t stream) {
-    const P3Shape s = p3_shape(h, w, nb, hs, ws);
+    const PyrBranches br = pyr_classify(h, w, nb, hs, ws);
+    const P3Shape s = p3_shape(h, w, br);
     MSPL_REQUIRE(s.ok, MSPL_ERR_UNSUPPORTED, "pyr_stream_tables: the streaming form does not cover a %dx%d map with these branches", h, w);
     MSPL_REQUIRE(bytes == (int64_t)(p3_table_floats(s, h) * sizeof(float)), MSPL_ERR_BAD_SHAPE,
                  "pyr_stream_tables: %lld bytes given, the geometry takes %zu", (long long)bytes, p3_table_floats(s, h) * sizeof(float));
     MSPL_REQUIRE((((uintptr_t)tab) & 15) == 0, MSPL_ERR_BAD_SHAPE, "pyr_stream_tables: the table must be 16-byte aligned");
     Pyr3Geom g;
-    p3_fill_geom(g, s, 0, 0, h, w, hs, ws);
+    p3_fill_geom(g, s, 0, 0, h, w, hs, ws, br);
     const int entries = 2 * (h + 2) * 3 + 2 * 3 * (s.ncb * 62 + 2) * s.PXL;
     const dim3 grid((unsigned)ceil_div(entries, 256)), blk(256);
 #define MSPL_P3_TABLES(A, B, L) hipLaunchKernelGGL((p3_tables_kernel<A, B, L>), grid, blk, 0, stream, g, tab)
-    if (s.PXL == 1) {
-        if (s.T0 == 3 && s.T1 == 3) MSPL_P3_TABLES(3, 3, 1);
-        else if (s.T0 == 3) MSPL_P3_TABLES(3, 5, 1);
-        else if (s.T1 == 3) MSPL_P3_TABLES(5, 3, 1);
-        else MSPL_P3_TABLES(5, 5, 1);
-    } else {
-        if (s.T0 == 3 && s.T1 == 3) MSPL_P3_TABLES(3, 3, 2);
-        else if (s.T0 == 3) MSPL_P3_TABLES(3, 5, 2);
-        else if (s.T1 == 3) MSPL_P3_TABLES(5, 3, 2);
-        else MSPL_P3_TABLES(5, 5, 2);
-    }
+    if (s.PXL == 1) MSPL_PYR_TAP_DISPATCH(s.T0, s.T1, MSPL_P3_TABLES, 1);
+    else MSPL_PYR_TAP_DISPATCH(s.T0, s.T1, MSPL_P3_TABLES, 2);
 #undef MSPL_P3_TABLES
     MSPL_CHECK_LAUNCH("pyr_stream_tables");
     std::lock_guard<std::mutex> lock(p3_tab_mutex);
@@ -607,12 +590,12 @@ int pyrpool_stream_tables_build(int h, int w, int nb, const int32_t* hs, const i
 }
 
 int64_t pyrpool_stream_tables_bytes(int h, int w, int nb, const int32_t* hs, const int32_t* ws) {
-    const P3Shape s = p3_shape(h, w, nb, hs, ws);
+    const P3Shape s = p3_shape(h, w, pyr_classify(h, w, nb, hs, ws));
     return s.ok ? (int64_t)(p3_table_floats(s, h) * sizeof(float)) : 0;
 }
 
 void pyrpool_stream_plan(int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws, int32_t* out) {
-    const P3Plan p = p3_plan(N, P, h, w, nb, hs, ws);
+    const P3Plan p = p3_plan(N, P, h, w, pyr_classify(h, w, nb, hs, ws));
     for (int i = 0; i < MSPL_PYR_STREAM_PLAN_LEN; ++i) out[i] = 0;
     if (!p.taken) return;
     out[MSPL_PYR_STREAM_PLAN_TAKEN] = 1;
@@ -624,13 +607,15 @@ void pyrpool_stream_plan(int N, int P, int h, int w, int nb, const int32_t* hs, 
     out[MSPL_PYR_STREAM_PLAN_WAVES_INKERNEL] = (int32_t)p.waves_ik;
 }
 
-// Returns MSPL_OK when launched, 1 when the shape is left to the LDS-tiled kernels, < 0 on error.  tab: geometry tables of
+// Returns MSPL_OK when launched, 1 when the shape is left to the LDS-tiled kernels, < 0 on error.  a.tab: geometry tables of
 // pyrpool_stream_tables_build, or null for the in-kernel tables; a table of another geometry is an error, nothing is launched.
-int pyrpool_stream_try(const float* x, int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws,
-                       const float* const* stage_w, const float* const* down_e, const float* br_scale,
-                       const float* br_shift, const float* br_alpha, const float* merge_w, const Epi& e, float* out,
-                       hipStream_t stream, float* zcat, const float* tab) {
-    const P3Plan plan = p3_plan(N, P, h, w, nb, hs, ws);
+int pyrpool_stream_try(const PyrFwdArgs& a) {
+    const int N = a.N, P = a.P, h = a.h, w = a.w;
+    const int32_t* hs = a.hs;  const int32_t* ws = a.ws;
+    const float* x = a.x;  const float* const* stage_w = a.stage_w;  const float* const* down_e = a.down_e;
+    float* out = a.out;  float* zcat = a.zcat;  const float* tab = a.tab;
+    const Epi& e = a.e;
+    const P3Plan plan = p3_plan(N, P, h, w, a.br);
     if (!plan.taken) return 1;
     const P3Shape& s = plan.s;
     if (tab) {
@@ -654,28 +639,19 @@ int pyrpool_stream_try(const float* x, int N, int P, int h, int w, int nb, const
     if (zcat && (!e.raw || e.ctot != P || e.coff != 0)) return 1;      // training forward: un-sliced destination + raw output
     if (zcat && PXL == 2 && ((((uintptr_t)zcat) | ((uintptr_t)e.raw)) & 7)) return 1;
     Pyr3Geom g;
-    p3_fill_geom(g, s, N, P, h, w, hs, ws);
+    p3_fill_geom(g, s, N, P, h, w, hs, ws, a.br);
     g.SEG = tab ? plan.seg_tab : plan.seg_ik;
     g.nseg = tab ? plan.nseg_tab : plan.nseg_ik;
     const int64_t waves = tab ? plan.waves_tab : plan.waves_ik;
     g.total = (unsigned)waves;
     const dim3 grid((unsigned)(waves / 4)), blk(256);          // workgroup = 4 consecutive planes of one (column block, segment)
-#define MSPL_P3_ARGS x, stage_w[0], stage_w[1], stage_w[2], down_e[3], down_e[4], br_scale, br_shift, br_alpha, merge_w, e.scale, e.shift, e.alpha, e.ctot, e.coff, g, out
+#define MSPL_P3_ARGS x, stage_w[0], stage_w[1], stage_w[2], down_e[3], down_e[4], a.br_scale, a.br_shift, a.br_alpha, a.merge_w, e.scale, e.shift, e.alpha, e.ctot, e.coff, g, out
 #define MSPL_P3_LAUNCH(A, B, L) do { \
-        if (zcat) hipLaunchKernelGGL((pyrpool_stream_kernel<A, B, L, true, false>), grid, blk, 0, stream, MSPL_P3_ARGS, zcat, e.raw, (const float*)nullptr); \
-        else if (tab) hipLaunchKernelGGL((pyrpool_stream_kernel<A, B, L, false, true>), grid, blk, 0, stream, MSPL_P3_ARGS, (float*)nullptr, (float*)nullptr, tab); \
-        else hipLaunchKernelGGL((pyrpool_stream_kernel<A, B, L, false, false>), grid, blk, 0, stream, MSPL_P3_ARGS, (float*)nullptr, (float*)nullptr, (const float*)nullptr); } while (0)
-    if (PXL == 1) {
-        if (s.T0 == 3 && s.T1 == 3) MSPL_P3_LAUNCH(3, 3, 1);
-        else if (s.T0 == 3) MSPL_P3_LAUNCH(3, 5, 1);
-        else if (s.T1 == 3) MSPL_P3_LAUNCH(5, 3, 1);
-        else MSPL_P3_LAUNCH(5, 5, 1);
-    } else {
-        if (s.T0 == 3 && s.T1 == 3) MSPL_P3_LAUNCH(3, 3, 2);
-        else if (s.T0 == 3) MSPL_P3_LAUNCH(3, 5, 2);
-        else if (s.T1 == 3) MSPL_P3_LAUNCH(5, 3, 2);
-        else MSPL_P3_LAUNCH(5, 5, 2);
-    }
+        if (zcat) hipLaunchKernelGGL((pyrpool_stream_kernel<A, B, L, true, false>), grid, blk, 0, a.stream, MSPL_P3_ARGS, zcat, e.raw, (const float*)nullptr); \
+        else if (tab) hipLaunchKernelGGL((pyrpool_stream_kernel<A, B, L, false, true>), grid, blk, 0, a.stream, MSPL_P3_ARGS, (float*)nullptr, (float*)nullptr, tab); \
+        else hipLaunchKernelGGL((pyrpool_stream_kernel<A, B, L, false, false>), grid, blk, 0, a.stream, MSPL_P3_ARGS, (float*)nullptr, (float*)nullptr, (const float*)nullptr); } while (0)
+    if (PXL == 1) MSPL_PYR_TAP_DISPATCH(s.T0, s.T1, MSPL_P3_LAUNCH, 1);
+    else MSPL_PYR_TAP_DISPATCH(s.T0, s.T1, MSPL_P3_LAUNCH, 2);
 #undef MSPL_P3_LAUNCH
 #undef MSPL_P3_ARGS
     MSPL_CHECK_LAUNCH("pyrpool_fused(streaming form)");

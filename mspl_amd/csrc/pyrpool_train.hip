@@ -15,7 +15,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
-#include "pyr_stencil.hpp"
+#include "pyr_geom.hpp"
 
 #include <type_traits>
 
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(256) void pyr_branch_bwd_kernel(const float* __rest
 
 
 // ------------------------------------------------------------------------------------------------ branch backward, streaming form
-// The same gradients from the separable-stencil view (pyr_stencil.hpp): with A_ky (rows) and G_kx (columns) the banded matrices of
+// The same gradients from the separable-stencil view (pyr_geom.hpp): with A_ky (rows) and G_kx (columns) the banded matrices of
 // a branch,   t = sum_ky sum_kx w[ky][kx] A_ky x G_kx^T   so
 //     gx          = sum_ky A_ky^T (gt C_ky),    C_ky = sum_kx w[ky][kx] G_kx          (T taps per row / column, T = 3 or 5)
 //     gw[ky][kx]  = < gt, A_ky x G_kx^T >
@@ -704,19 +704,12 @@ static bool pyr_branch_bwd_stream_shape(int N, int P, int h, int w, int hs, int 
     static const int off = (MSPL_TUNE_INT("MSPL_PYR_BWD_STREAM", 1) == 0);
     if (off || (w & 1) || ((int64_t)N * P) % 4 != 0 || hs < h || ws < w || h < 2 || w < 2) return false;
     // (a branch of the map's own size is the plain 3x3: its coefficient tables have one unit entry inside the 3-tap band)
-    const int Rr = (hs == h && ws == w) ? 1 : std::max(p3_stencil_radius(h, hs), p3_stencil_radius(w, ws));
-    if (Rr > 2) return false;
-    taps = Rr <= 1 ? 3 : 5;
+    taps = (hs == h && ws == w) ? 3 : pyr_up_taps(h, w, hs, ws);
+    if (taps == 0) return false;
     return sb_split(N, P, h, w, sp);
 }
 
-// 0 = launched, 1 = shape not covered by the streaming form, < 0 error
-static int pyr_branch_bwd_stream_try(const float* x, const float* gt, const float* wst, const float* add0, const float* add1, int N,
-                                     int P, int h, int w, int hs, int ws, int accumulate, float* gx, float* gw, hipStream_t stream) {
-    int taps;
-    SbSplit sp;
-    if (!pyr_branch_bwd_stream_shape(N, P, h, w, hs, ws, taps, sp)) return 1;
-    if ((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1)) & 7) return 1;
+static SbGeom sb_geom(int N, int P, int h, int w, int hs, int ws, const SbSplit& sp, int accumulate) {
     SbGeom g;
     memset(&g, 0, sizeof(g));
     g.N = N; g.P = P; g.h = h; g.w = w; g.hs = hs; g.ws = ws;
@@ -726,6 +719,17 @@ static int pyr_branch_bwd_stream_try(const float* x, const float* gt, const floa
     g.SEG = sp.seg;
     g.nseg = sp.nseg;
     g.accumulate = accumulate;
+    return g;
+}
+
+// 0 = launched, 1 = shape not covered by the streaming form, < 0 error
+static int pyr_branch_bwd_stream_try(const float* x, const float* gt, const float* wst, const float* add0, const float* add1, int N,
+                                     int P, int h, int w, int hs, int ws, int accumulate, float* gx, float* gw, hipStream_t stream) {
+    int taps;
+    SbSplit sp;
+    if (!pyr_branch_bwd_stream_shape(N, P, h, w, hs, ws, taps, sp)) return 1;
+    if ((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1)) & 7) return 1;
+    const SbGeom g = sb_geom(N, P, h, w, hs, ws, sp, accumulate);
     const int64_t waves = (int64_t)N * P * g.ncb * g.nseg;
     const dim3 grid((unsigned)(waves / 4)), blk(256);
     if (taps == 3) hipLaunchKernelGGL(pyr_branch_bwd_stream_kernel<3>, grid, blk, 0, stream, x, gt, wst, add0, add1, g, gx, gw);
@@ -947,19 +951,18 @@ __global__ __launch_bounds__(256) void pyr_branch_bwd_stream3_kernel(const float
 }
 
 // the shapes the all-branches streaming form covers (operand alignment aside): [up, up, same], [up, same], [up, up] or [up]
-static bool pyr_branch_bwd_stream3_shape(int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws, int (&taps)[2],
-                                         bool& same, int& nup, SbSplit& sp) {
+static bool pyr_branch_bwd_stream3_shape(int N, int P, int h, int w, const PyrBranches& br, int (&taps)[2], bool& same, int& nup,
+                                         SbSplit& sp) {
     static const int off = (MSPL_TUNE_INT("MSPL_PYR_BWD_STREAM3", 1) == 0);
+    const int nb = br.nb;
     if (off || (w & 1) || w < 2 || h < 2 || ((int64_t)N * P) % 4 != 0 || nb < 1 || nb > 3) return false;
-    same = hs[nb - 1] == h && ws[nb - 1] == w;
+    same = br.kind[nb - 1] == PYR_SAME;
     nup = nb - (same ? 1 : 0);
     if (nup < 1 || nup > 2) return false;
     taps[0] = taps[1] = 3;
     for (int i = 0; i < nup; ++i) {
-        if (hs[i] < h || ws[i] < w || (hs[i] == h && ws[i] == w)) return false;
-        const int Rr = std::max(p3_stencil_radius(h, hs[i]), p3_stencil_radius(w, ws[i]));
-        if (Rr > 2) return false;
-        taps[i] = Rr <= 1 ? 3 : 5;
+        if (br.kind[i] != PYR_UP || br.taps[i] == 0) return false;
+        taps[i] = br.taps[i];
     }
     return sb_split(N, P, h, w, sp);
 }
@@ -971,20 +974,13 @@ static int pyr_branch_bwd_stream3_try(const float* x, int N, int P, int h, int w
     int taps[2], nup;
     bool same;
     SbSplit sp;
-    if (!pyr_branch_bwd_stream3_shape(N, P, h, w, nb, hs, ws, taps, same, nup, sp)) return 1;
+    if (!pyr_branch_bwd_stream3_shape(N, P, h, w, pyr_classify(h, w, nb, hs, ws), taps, same, nup, sp)) return 1;
     if ((((uintptr_t)gx) | ((uintptr_t)add0) | ((uintptr_t)add1) | ((uintptr_t)x)) & 7) return 1;
     for (int i = 0; i < nb; ++i)
         if ((((uintptr_t)gt[i]) & 7)) return 1;
-    SbGeom g;
-    memset(&g, 0, sizeof(g));
-    g.N = N; g.P = P; g.h = h; g.w = w; g.hs = hs[0]; g.ws = ws[0];
-    g.sh = bilinear_scale(h, hs[0]); g.sw = bilinear_scale(w, ws[0]);
+    const SbGeom g = sb_geom(N, P, h, w, hs[0], ws[0], sp, 0);
     const int hs1 = nup > 1 ? hs[1] : hs[0], ws1 = nup > 1 ? ws[1] : ws[0];
     const float sh1 = bilinear_scale(h, hs1), sw1 = bilinear_scale(w, ws1);
-    g.CBW = SB_CBW;
-    g.ncb = sp.ncb;
-    g.SEG = sp.seg;
-    g.nseg = sp.nseg;
     const int64_t waves = (int64_t)N * P * g.ncb * g.nseg;
     const dim3 grid((unsigned)(waves / 4)), blk(256);
     const float* g1 = nup > 1 ? gt[1] : gt[0];
@@ -994,21 +990,10 @@ static int pyr_branch_bwd_stream3_try(const float* x, int N, int P, int h, int w
     float* o1 = nup > 1 ? gw[1] : gw[0];
     float* o2 = same ? gw[nb - 1] : gw[0];
 #define MSPL_SB3(A, B, U, S) hipLaunchKernelGGL((pyr_branch_bwd_stream3_kernel<A, B, U, S>), grid, blk, 0, stream, x, gt[0], g1, g2, stage_w[0], s1, s2, add0, add1, g, hs1, ws1, sh1, sw1, gx, gw[0], o1, o2)
-    if (nup == 2 && same) {
-        if (taps[0] == 3 && taps[1] == 5) MSPL_SB3(3, 5, 2, true);
-        else if (taps[0] == 3 && taps[1] == 3) MSPL_SB3(3, 3, 2, true);
-        else if (taps[0] == 5 && taps[1] == 5) MSPL_SB3(5, 5, 2, true);
-        else MSPL_SB3(5, 3, 2, true);
-    } else if (nup == 2) {
-        if (taps[0] == 3 && taps[1] == 5) MSPL_SB3(3, 5, 2, false);
-        else if (taps[0] == 3 && taps[1] == 3) MSPL_SB3(3, 3, 2, false);
-        else if (taps[0] == 5 && taps[1] == 5) MSPL_SB3(5, 5, 2, false);
-        else MSPL_SB3(5, 3, 2, false);
-    } else if (same) {
-        if (taps[0] == 3) MSPL_SB3(3, 3, 1, true); else MSPL_SB3(5, 3, 1, true);
-    } else {
-        if (taps[0] == 3) MSPL_SB3(3, 3, 1, false); else MSPL_SB3(5, 3, 1, false);
-    }
+    if (nup == 2 && same) MSPL_PYR_TAP_DISPATCH(taps[0], taps[1], MSPL_SB3, 2, true);
+    else if (nup == 2) MSPL_PYR_TAP_DISPATCH(taps[0], taps[1], MSPL_SB3, 2, false);
+    else if (same) MSPL_PYR_TAP_DISPATCH_1UP(taps[0], MSPL_SB3, 1, true);
+    else MSPL_PYR_TAP_DISPATCH_1UP(taps[0], MSPL_SB3, 1, false);
 #undef MSPL_SB3
     MSPL_CHECK_LAUNCH("pyrpool_branch_bwd(streaming, all branches)");
     return 0;
@@ -1057,7 +1042,8 @@ extern "C" int mspl_pyrpool_merge_bwd(const float* gy, const float* mraw, const 
 }
 
 // host-side plan of the branch-backward tiles; returns the LDS bytes, 0 when a branch is not covered
-static size_t ub_plan(int N, int P, int h, int w, int nb, const int32_t* hs, const int32_t* ws, UbGeom& g) {
+static size_t ub_plan(int N, int P, int h, int w, const int32_t* hs, const int32_t* ws, const PyrBranches& br, UbGeom& g) {
+    const int nb = br.nb;
     if (nb < 1 || nb > UB_MAXB || h < 2 || w < 2) return 0;
     memset(&g, 0, sizeof(g));
     g.N = N; g.P = P; g.h = h; g.w = w; g.nb = nb;
@@ -1065,10 +1051,10 @@ static size_t ub_plan(int N, int P, int h, int w, int nb, const int32_t* hs, con
     int max_u = 0, max_g = 0, max_tab = 0;
     for (int i = 0; i < nb; ++i) {
         UbBranch& B = g.b[i];
-        if (hs[i] < h || ws[i] < w || hs[i] < 2 || ws[i] < 2) return 0;
+        if (br.kind[i] > PYR_SAME || hs[i] < 2 || ws[i] < 2) return 0;                 // up-sampled or same-size branches only
         if ((int64_t)(hs[i] - 1) > 3ll * (h - 1) || (int64_t)(ws[i] - 1) > 3ll * (w - 1)) return 0;   // <= 8 grid rows per x row (UB_KG)
         B.hs = hs[i]; B.ws = ws[i];
-        B.sh = bilinear_scale(h, hs[i]); B.sw = bilinear_scale(w, ws[i]);
+        B.sh = br.sh[i]; B.sw = br.sw[i];
         // grid rows that can touch the x rows [y0 - 1, y0 + TH]: (TH + 2) / s + slack, plus the one-point halo on both sides
         B.UHT = (int)((double)(UB_TH + 2) / (double)B.sh) + 6;
         B.UWT = (int)((double)(UB_TW + 2) / (double)B.sw) + 6;
@@ -1107,11 +1093,12 @@ static void pyr_branch_bwd_plan(int N, int P, int h, int w, int nb, const int32_
     memset(&p, 0, sizeof(p));
     p.form = MSPL_PYR_BRANCH_BWD_UNSUPPORTED;
     if (N <= 0 || P <= 0 || nb < 1 || nb > UB_MAXB) return;
+    const PyrBranches br = pyr_classify(h, w, nb, hs, ws);
     SbSplit sp;
     {   // every branch in one walk (the standard [up, up, same] pattern)
         int taps[2], nup;
         bool same;
-        if (al_out && al_in && pyr_branch_bwd_stream3_shape(N, P, h, w, nb, hs, ws, taps, same, nup, sp)) {
+        if (al_out && al_in && pyr_branch_bwd_stream3_shape(N, P, h, w, br, taps, same, nup, sp)) {
             p.form = MSPL_PYR_BRANCH_BWD_STREAM3;
             p.ncb = sp.ncb; p.nseg = sp.nseg; p.seg = sp.seg;
             for (int i = 0; i < nup; ++i) p.taps[i] = taps[i];
@@ -1130,7 +1117,7 @@ static void pyr_branch_bwd_plan(int N, int P, int h, int w, int nb, const int32_
             return;
         }
     }
-    p.lds = ub_plan(N, P, h, w, nb, hs, ws, p.ub);
+    p.lds = ub_plan(N, P, h, w, hs, ws, br, p.ub);
     if (p.lds > 0 && p.lds <= 64 * 1024 && (int64_t)N * P * p.ub.tiles_y < (1ll << 31)) {
         p.form = MSPL_PYR_BRANCH_BWD_TILE;
         p.tiles_x = p.ub.tiles_x; p.tiles_y = p.ub.tiles_y;

@@ -347,6 +347,7 @@ __global__ __launch_bounds__(256) void bilinear_stream_kernel(const float* __res
     }
 }
 
+// (64-bit products, for maps of any size: other instructions than the 32-bit pyr_bin_s / pyr_bin_e of pyr_geom.hpp, so kept apart)
 __device__ __forceinline__ int ada_start(int o, int I, int O) { return (int)(((int64_t)o * I) / O); }
 __device__ __forceinline__ int ada_end(int o, int I, int O) { return (int)((((int64_t)(o + 1)) * I + O - 1) / O); }
 

@@ -102,14 +102,14 @@ OPS = {
         entry='mspl_pyrpool_fused_fwd', accepts=ALL | {'slice'}, refuses=frozenset({'raw_out'}),
         termsets=('singles', AFFINE, ALL),
         # (N, P, h, w) of the projected map; branch sizes by EfficientPyrPool.branch_sizes
-        cases=[Case((1, 4, 6, 9), 'separable LDS form with AFFINE, table form otherwise', 'pyrpool_sep.hip:483'),
-               Case((2, 8, 14, 22), 'separable LDS form with AFFINE, table form otherwise', 'pyrpool_sep.hip:483'),
-               Case((2, 16, 33, 47), 'streaming form with AFFINE, table form otherwise', 'pyrpool_stream.hip:399', 5.5e-6)]),
+        cases=[Case((1, 4, 6, 9), 'separable LDS form with AFFINE, table form otherwise', 'pyrpool_sep.hip:457'),
+               Case((2, 8, 14, 22), 'separable LDS form with AFFINE, table form otherwise', 'pyrpool_sep.hip:457'),
+               Case((2, 16, 33, 47), 'streaming form with AFFINE, table form otherwise', 'pyrpool_stream.hip:635', 5.5e-6)]),
     'pyrpool_fused_train': dict(
         entry='mspl_pyrpool_fused_train_fwd', accepts=EVERYTHING, refuses=frozenset(),
         termsets=(AFFINE, ALL),
-        cases=[Case((1, 4, 6, 9), 'table form (narrower than the streaming form takes)', 'pyrpool_stream.hip:398'),
-               Case((2, 16, 33, 47), 'streaming form with AFFINE + raw_out, table form otherwise', 'pyrpool_stream.hip:414')]),
+        cases=[Case((1, 4, 6, 9), 'table form (narrower than the streaming form takes)', 'pyrpool_stream.hip:495'),
+               Case((2, 16, 33, 47), 'streaming form with AFFINE + raw_out, table form otherwise', 'pyrpool_stream.hip:639')]),
     # ---- entry points that implement scale / shift / alpha and refuse the rest
     'eesp_dw_hff': dict(
         entry='mspl_eesp_dw_hff_fwd', accepts=AFFINE | {'slice', 'raw_out'}, refuses=ALL - AFFINE,
