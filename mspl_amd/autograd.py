@@ -215,7 +215,7 @@ class WeightTransposer(object):
         # every copy starts at a multiple of 4 floats: the 1x1 kernels read weights as 16-byte vectors (an unaligned weight
         # tensor drops the data-gradient convolution to the slower generic kernel)
         self.flat = torch.empty(max(sum(_align4(w.numel()) for w, _, _ in items), 1), device=dev, dtype=torch.float32)
-        raw = np.zeros((max(len(items), 1), 10), dtype=np.int32)        # struct WtSeg (train.hip): 2 pointers + 6 int32 = 40 bytes
+        raw = np.zeros((max(len(items), 1), 10), dtype=np.int32)        # struct WtSeg (conv_bwd.hip): 2 pointers + 6 int32 = 40 bytes
         blocks, self.lookup, off = [], {}, 0
         for i, (w, groups, k) in enumerate(items):
             cout, cin_g = w.shape[0], w.shape[1]

@@ -90,6 +90,13 @@ static inline unsigned xcd_per(int64_t total) { return (unsigned)((total + 7) / 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Grid of a kernel that reads its plane as blockIdx.z * gridDim.y + blockIdx.y: gx workgroups per plane, the planes on y and, past
+// 65535 of them, in rounds of 65535 on z (the last round may run past `planes`: the kernel checks).  The caller bounds `planes`.
+static inline dim3 plane_grid(int gx, int64_t planes) {
+    const int64_t gy = planes < 65535 ? planes : 65535;
+    return dim3((unsigned)gx, (unsigned)gy, (unsigned)ceil_div64(planes, gy));
+}
+
 // ------------------------------------------------------------------ device epilogue
 // Device copy of mspl_epilogue_t with the destination geometry resolved.
 struct Epi {

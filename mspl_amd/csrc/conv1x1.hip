@@ -882,8 +882,8 @@ static int plan_thin(const PwFacts& f, PwPlan& p) {
     if (p.lds > 48 * 1024) return 1;
     const int64_t slabs = (int64_t)f.N * f.G;
     if (slabs >= 65535ll * 65535ll) return 1;
-    const int gy = slabs < 65535 ? (int)slabs : 65535;
-    p.gx = (unsigned)ceil_div(g.Q, 256); p.gy = (unsigned)gy; p.gz = (unsigned)ceil_div64(slabs, gy);
+    const dim3 grid = plane_grid(ceil_div(g.Q, 256), slabs);
+    p.gx = grid.x; p.gy = grid.y; p.gz = grid.z;
     return 0;
 }
 
@@ -1053,8 +1053,8 @@ static int plan_small(const PwFacts& f, PwPlan& p) {
     MSPL_REQUIRE(p.lds <= 48 * 1024, MSPL_ERR_UNSUPPORTED, "conv1x1(small-K): weight block %zu B exceeds LDS", p.lds);
     const int64_t slabs = (int64_t)f.N * f.G * g.mtiles;
     MSPL_REQUIRE(slabs < 65535ll * 65535ll, MSPL_ERR_BAD_SHAPE, "conv1x1: grid too large");
-    const int gy = slabs < 65535 ? (int)slabs : 65535;
-    p.gx = (unsigned)ceil_div(g.Q, 256); p.gy = (unsigned)gy; p.gz = (unsigned)ceil_div64(slabs, gy);
+    const dim3 grid = plane_grid(ceil_div(g.Q, 256), slabs);
+    p.gx = grid.x; p.gy = grid.y; p.gz = grid.z;
     return MSPL_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "conv1x1_wgrad.hpp"
 
 namespace mspl {
 

@@ -2,7 +2,7 @@
 //   PixelwiseKLD.forward                       :181-189   kld[n,p] = sum_c softmax(d1)_c * (log_softmax(d1)_c - log_softmax(d2)_c)
 //   UncertaintyWeightedSegmentationLoss.forward :155-175   mean_{n,p}( w[t] * -log_softmax(pred)[t] * exp(-u) )   (mean over ALL pixels)
 //   SegmentationLoss (loss_type 'ce')          :11-52     nn.CrossEntropyLoss(weight, ignore_index): sum(w[t]*nll) / sum_{valid}(w[t])
-// The fused K11 kernel (train.hip) covers the exact uest combination in one pass; these serve callers that compose
+// The fused K11 kernel (uw_loss.hip) covers the exact uest combination in one pass; these serve callers that compose
 // the modules themselves.  One thread per pixel; the cross entropy streams the classes with a running log-sum-exp, the KL takes each
 // head's maximum first (lsm_norm); NCHW fp32, int64 targets.
 #include <algorithm>

@@ -35,9 +35,7 @@ __device__ __forceinline__ bool strip_decode(const RsGeom& g, int& n, int& c, in
 }
 
 static inline dim3 strip_grid(const RsGeom& g) {
-    const int planes = g.N * g.C;
-    const int gy = planes < 65535 ? planes : 65535;
-    return dim3((unsigned)ceil_div(g.Ho * g.XS, 256), (unsigned)gy, (unsigned)ceil_div(planes, gy));
+    return plane_grid(ceil_div(g.Ho * g.XS, 256), g.N * g.C);
 }
 
 __device__ __forceinline__ void strip_store(const Epi& e, const RsGeom& g, int n, int c, int y, int x0,
@@ -605,8 +603,7 @@ extern "C" int mspl_pointwise_fwd(const float* x, int32_t N, int32_t C, int32_t 
     MSPL_REQUIRE(N > 0 && C > 0 && HW > 0, MSPL_ERR_BAD_SHAPE, "pointwise: bad shape N=%d C=%d HW=%d", N, C, HW);
     if (int rc = check_epi(ep, C, "pointwise")) return rc;
     const Epi e = make_epi(ep, C, HW);
-    const int planes = N * C, gy = planes < 65535 ? planes : 65535;
-    const dim3 grid((unsigned)ceil_div((HW + 3) / 4, 256), (unsigned)gy, (unsigned)ceil_div(planes, gy));
+    const dim3 grid = plane_grid(ceil_div((HW + 3) / 4, 256), N * C);
     hipLaunchKernelGGL(pointwise_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, N, C, e, out);
     MSPL_CHECK_LAUNCH("pointwise");
     return MSPL_OK;

@@ -762,8 +762,7 @@ extern "C" int mspl_bn_train_prelu_bwd_apply(const float* z, const float* gy, co
     const int L = vec ? HW / 4 : HW;
     const int64_t planes = (int64_t)N * C;
     MSPL_REQUIRE(planes <= 65535ll * 65535ll, MSPL_ERR_BAD_SHAPE, "bn_train_prelu_bwd_apply: too many planes");
-    const int gy_ = planes < 65535 ? (int)planes : 65535;
-    const dim3 grid((unsigned)ceil_div(L, 256), (unsigned)gy_, (unsigned)ceil_div64(planes, gy_));
+    const dim3 grid = plane_grid(ceil_div(L, 256), planes);
     if (vec) hipLaunchKernelGGL(bn_train_bwd_apply_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, z, gy, scale, shift, alpha, p, q, (long long)planes, C, L, gz);
     else hipLaunchKernelGGL(bn_train_bwd_apply_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, z, gy, scale, shift, alpha, p, q, (long long)planes, C, L, gz);
     MSPL_CHECK_LAUNCH("bn_train_prelu_bwd_apply");
@@ -800,8 +799,7 @@ extern "C" int mspl_bn_stats_path_add(float* g, const float* z, const float* p, 
     MSPL_REQUIRE((((uintptr_t)g | (uintptr_t)z) & 15) == 0, MSPL_ERR_BAD_SHAPE, "bn_stats_path_add: operands must be 16-byte aligned");
     const int64_t planes = (int64_t)nb * N * P;
     MSPL_REQUIRE(planes <= 65535ll * 65535ll, MSPL_ERR_BAD_SHAPE, "bn_stats_path_add: too many planes");
-    const int gy = planes < 65535 ? (int)planes : 65535;
-    const dim3 grid((unsigned)ceil_div(HW / 4, 256), (unsigned)gy, (unsigned)ceil_div64(planes, gy));
+    const dim3 grid = plane_grid(ceil_div(HW / 4, 256), planes);
     hipLaunchKernelGGL(bn_stats_path_add_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, z, p, q, N, P, nb, HW / 4);
     MSPL_CHECK_LAUNCH("bn_stats_path_add");
     return MSPL_OK;

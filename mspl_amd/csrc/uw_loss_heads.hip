@@ -6,7 +6,7 @@
 // back: 75 + 47 us of a 6.7 ms step at 16 x 5 x 288x480.  Here a workgroup owns a band of TH rows x 256 columns of the label map: it
 // stages the patches of both low-resolution maps that band interpolates from in LDS and evaluates the up-sampled logits per pixel
 // with the reference's own expression (wy0 * (wx0 * a + wx1 * b) + wy1 * (...): the forward is the one mspl_resize_bilinear
-// computes), the loss terms and the closed-form gradients of uw_loss_kernel (train.hip).  The gradients leave at label resolution
+// computes), the loss terms and the closed-form gradients of uw_loss_kernel (uw_loss.hip).  The gradients leave at label resolution
 // (N,C,H,W), for mspl_bilinear_bwd: the full-size logits never exist.
 //
 // (Measured and not kept, round 5: the transposed interpolation inside this kernel as ds_add_f32 into LDS accumulators of the patches'
@@ -227,7 +227,7 @@ static int uh_launch(const float* main_lo, const float* aux_lo, const int64_t* t
     g.total = (unsigned)tiles;
     g.ce_scale = ce_scale;
     g.inv_npix = out_scale / (float)((int64_t)N * H * W);
-    // one same-address atomic per workgroup on the loss: a bounded grid walks the tiles (train.hip, uw_loss_launch)
+    // one same-address atomic per workgroup on the loss: a bounded grid walks the tiles (uw_loss.hip, uw_loss_launch)
     const unsigned blocks = (unsigned)std::min<int64_t>(tiles, 1536);
     hipStream_t s = (hipStream_t)stream;
     static std::once_flag once;

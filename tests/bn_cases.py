@@ -1,7 +1,7 @@
 """Inputs, the float64 oracle and the bounds of the batch-statistics BatchNorm kernels at ill-conditioned channels and at the seams
 between their forms (a helper, no tests).
 
-The three forms (mspl_amd/csrc/supervised.hip, train.hip): the small-plane node (one workgroup per channel), the fused two-launch
+The three forms (mspl_amd/csrc/supervised.hip, affine_bwd.hip): the small-plane node (one workgroup per channel), the fused two-launch
 node (`parts` ranges per channel, persistent workspace) and the plain statistics pair behind autograd.bn_batch_stats.  The reference
 is `bn_train_prelu_oracle` on `.double()` inputs; the yardstick of every bound is the SAME oracle on the float32 inputs on the CPU
 against its float64 result (`err32`) and the rounding of float32 (FLOOR) times a magnitude taken from float64 -- never the code under

@@ -1,43 +1,29 @@
 #!/usr/bin/env python3
-"""Do the kernels of a .hip file compile to the same code as at another revision?  For a refactor that must not touch device code.
+"""Do the kernels of the library compile to the same code as at another revision?  For a refactor that must not touch device code.
 
-    python tools/kernel_isa_diff.py REV [file.hip ...]        (default: every .hip of mspl_amd/csrc)
+    python tools/kernel_isa_diff.py REV [file.hip ...]        (default: every .hip of mspl_amd/csrc, on both sides)
 
 mspl_amd/csrc and include of REV are extracted into a temporary directory; each file is compiled there and in the working tree to
-device-only assembly (--cuda-device-only -S) with the flags that tree's own Makefile gives it (read from `make -n`).  Per kernel
-three texts are compared: the instructions between its label and its .Lfunc_end (comments and blank lines stripped, the function
-number inside local labels -- .LBB<n>_<k> -- dropped: it only counts the functions ahead of it in the file), its .amdhsa_kernel
-descriptor (registers, LDS, scratch, kernarg size) and its entry in the amdhsa.kernels metadata.  One line per kernel that differs
-or exists on one side only, then a count; the exit status is the number of such kernels (capped at 255)."""
+device-only assembly (--cuda-device-only -S) with the flags that tree's own Makefile gives it (tools/build_flags.py).  Kernels are
+matched BY SYMBOL across all files of a side, so a kernel may move between files (a named file is compiled on every side that has
+it).  Per kernel three texts are compared: the instructions between its label and its .Lfunc_end (comments and blank lines stripped,
+the function number inside local labels -- .LBB<n>_<k> -- dropped: it only counts the functions ahead of it in the file), its
+.amdhsa_kernel descriptor (registers, LDS, scratch, kernarg size) and its entry in the amdhsa.kernels metadata.  One line per kernel
+that differs or exists on one side only, one per kernel that moved, then a count; the exit status is the number of kernels that
+differ or exist on one side only (capped at 255).  A symbol defined in two files of one side is an error, except a kernel with
+internal linkage (a static one in a shared header), which is matched within its file."""
 import os
 import re
-import shlex
 import subprocess
 import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join('mspl_amd', 'csrc')
-
-
-def compile_lines(tree):
-    """{file.hip: argv} of the Makefile's compile commands in `tree`."""
-    txt = subprocess.run(['make', '-n', '-B', '-C', os.path.join(tree, CSRC)], capture_output=True, text=True, check=True).stdout
-    out = {}
-    for line in txt.splitlines():
-        argv = shlex.split(line)
-        if '-c' in argv and argv[argv.index('-c') + 1].endswith('.hip'):
-            out[argv[argv.index('-c') + 1]] = argv
-    return out
+from build_flags import CSRC, ROOT, compile_lines, device_only
 
 
 def assembly(tree, name, argv, dst):
-    argv = list(argv)
-    k = argv.index('-c')
-    argv[k:k + 2] = ['--cuda-device-only', '-S', name]
-    argv[argv.index('-o') + 1] = dst
-    r = subprocess.run(argv, cwd=os.path.join(tree, CSRC), capture_output=True, text=True)
+    r = subprocess.run(device_only(argv, '-S', dst), cwd=os.path.join(tree, CSRC), capture_output=True, text=True)
     if r.returncode:
         sys.exit('%s in %s:\n%s' % (name, tree, r.stderr[-4000:]))
     with open(dst) as f:
@@ -72,6 +58,36 @@ def kernels(asm):
     return {s: (body[s], desc[s], meta.get(s, '')) for s in desc}
 
 
+def internal_linkage(sym):
+    """_ZL<name> or _ZN<len><name>...L<len><name>: walks the length-prefixed components of the nested name."""
+    if not sym.startswith('_ZN'):
+        return sym.startswith('_ZL')
+    k = 3
+    while k < len(sym):
+        m = re.match(r'\d+', sym[k:])
+        if not m:
+            return sym[k] == 'L' and sym[k + 1:k + 2].isdigit()
+        k += len(m.group(0)) + int(m.group(0))
+    return False
+
+
+def side(tree, label, cmds, files, tmp):
+    """{symbol: (file, texts)} over `files` of one side.  A kernel with internal linkage (a static one in a header that several files
+    include; its mangled name carries an L before the length) stays with its file, as 'file:symbol'."""
+    jobs = [(tree, f, cmds[f], os.path.join(tmp, '%s_%s.s' % (label, f))) for f in files]
+    with ThreadPoolExecutor(16) as ex:
+        per_file = list(ex.map(lambda j: kernels(assembly(*j)), jobs))
+    out = {}
+    for f, ks in zip(files, per_file):
+        for sym, texts in ks.items():
+            if internal_linkage(sym):
+                sym = '%s:%s' % (f, sym)
+            if sym in out:
+                sys.exit('%s: %s is defined in %s and in %s' % (label, sym, out[sym][0], f))
+            out[sym] = (f, texts)
+    return out
+
+
 def main():
     if len(sys.argv) < 2:
         sys.exit(__doc__)
@@ -82,29 +98,28 @@ def main():
         tar = subprocess.run(['git', '-C', ROOT, 'archive', rev, CSRC, 'include'], capture_output=True, check=True).stdout
         subprocess.run(['tar', '-x', '-C', old], input=tar, check=True)
         cmd_old, cmd_new = compile_lines(old), compile_lines(ROOT)
-        files = [os.path.basename(f) for f in sys.argv[2:]] or sorted(set(cmd_old) | set(cmd_new))
-        jobs = []
-        for f in files:
-            if f not in cmd_old or f not in cmd_new:
-                print('%-24s only in %s' % (f, 'the working tree' if f in cmd_new else rev))
-                continue
-            jobs.append((old, f, cmd_old[f], os.path.join(tmp, 'old_' + f + '.s')))
-            jobs.append((ROOT, f, cmd_new[f], os.path.join(tmp, 'new_' + f + '.s')))
-        with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
-            asm = list(ex.map(lambda j: kernels(assembly(*j)), jobs))
-        bad = total = 0
-        for k in range(0, len(jobs), 2):
-            f, ko, kn = jobs[k][1], asm[k], asm[k + 1]
-            for sym in sorted(set(ko) | set(kn)):
-                total += 1
-                if sym not in ko or sym not in kn:
-                    what = ['only in ' + (rev if sym in ko else 'the working tree')]
-                else:
-                    what = [n for n, a, b in zip(('instructions', 'descriptor', 'metadata'), ko[sym], kn[sym]) if a != b]
-                if what:
-                    bad += 1
-                    print('%-24s %s: %s' % (f, sym, ', '.join(what)))
-        print('%d of %d kernels in %d files differ from %s' % (bad, total, len(jobs) // 2, rev))
+        named = [os.path.basename(f) for f in sys.argv[2:]]
+        for f in named:
+            if f not in cmd_old and f not in cmd_new:
+                sys.exit('%s is in neither tree' % f)
+        ko = side(old, 'old', cmd_old, sorted(f for f in cmd_old if not named or f in named), tmp)
+        kn = side(ROOT, 'new', cmd_new, sorted(f for f in cmd_new if not named or f in named), tmp)
+        bad = moved = 0
+        for sym in sorted(set(ko) | set(kn)):
+            if sym not in ko or sym not in kn:
+                f = (ko.get(sym) or kn[sym])[0]
+                what = ['only in ' + (rev if sym in ko else 'the working tree')]
+            else:
+                fo, fn = ko[sym][0], kn[sym][0]
+                f = fo if fo == fn else '%s -> %s' % (fo, fn)
+                moved += fo != fn
+                what = [n for n, a, b in zip(('instructions', 'descriptor', 'metadata'), ko[sym][1], kn[sym][1]) if a != b]
+            if what:
+                bad += 1
+            if what or ' -> ' in f:
+                print('%-40s %s: %s' % (f, sym, ', '.join(what) or 'moved, identical'))
+        print('%d of %d kernels differ from %s (%d files there, %d here); %d moved to another file' % (
+            bad, len(set(ko) | set(kn)), rev, len({v[0] for v in ko.values()}), len({v[0] for v in kn.values()}), moved))
         sys.exit(min(bad, 255))
 
 

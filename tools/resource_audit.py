@@ -1,23 +1,23 @@
 #!/usr/bin/env python3
-"""Register / occupancy audit of every kernel: compiles each .hip with -Rpass-analysis=kernel-resource-usage (device only) and lists the
-kernels with VGPR spills, > 20 spilled SGPRs or <= 2 waves per SIMD.  Usage: python tools/resource_audit.py [all]"""
-import glob, os, re, subprocess, sys
+"""Register / occupancy audit of every kernel: compiles each .hip with -Rpass-analysis=kernel-resource-usage (device only, with the
+flags the Makefile gives that file: tools/build_flags.py) and lists the kernels with VGPR spills, > 20 spilled SGPRs or <= 2 waves
+per SIMD.  Usage: python tools/resource_audit.py [all]"""
+import os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
-root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'mspl_amd', 'csrc')
-NOSLP = {'pyrpool_sep.hip', 'eesp_dw.hip', 'pyrpool_stream.hip', 'pyrpool_train.hip', 'train.hip'}      # as in the Makefile
+
+from build_flags import CSRC, ROOT, compile_lines, device_only
 
 
-def one(f):
-    ex = ['-fno-slp-vectorize'] if os.path.basename(f) in NOSLP else []
-    r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', *ex,
-                        '--cuda-device-only', '-c', f, '-o', '/dev/null', '-Rpass-analysis=kernel-resource-usage'],
-                       capture_output=True, text=True, cwd=root)
+def one(item):
+    f, argv = item
+    r = subprocess.run(device_only(argv, '-c', '/dev/null', ['-Rpass-analysis=kernel-resource-usage']), capture_output=True, text=True,
+                       cwd=os.path.join(ROOT, CSRC))
     return f, r.stderr
 
 
 rows = []
 with ThreadPoolExecutor(8) as ex:
-    for f, txt in ex.map(one, sorted(glob.glob(os.path.join(root, '*.hip')))):
+    for f, txt in ex.map(one, sorted(compile_lines().items())):
         cur = None
         for l in txt.splitlines():
             m = re.search(r'remark:\s+(.*?)\s*\[-Rpass', l)
